@@ -8,11 +8,17 @@ reference's PartialModel.serialized_model + deserialized_model pair (SURVEY.md Â
 
 Workload (BASELINE.json north_star): the 64 MiB fp32 tensor, N = 16,777,216, alpha = 0.01 ->
 k = 167,772 â€” the configuration the north-star target (>= 50 % of HBM peak) is quoted on.  The
-C2 tensor (configs[1], N = 11,000,000, ResNet-18-sized) runs beside it as the `secondary` object.
+C2 tensor (configs[1], N = 11,000,000, ResNet-18-sized) runs beside it as the `secondary` object
+(--full).
 Multi-GPU (torchrun): each rank encodes+decodes its own node's tensor (the gossip round is a set
 of independent per-node codecs: no data-path collective) -> weak scaling; value = all ranks'
-params / max-over-ranks time.  Beside it, every run times one C4 gossip round of the 96-node
+params / max-over-ranks time.  Beside it, a --full run times one C4 gossip round of the 96-node
 topology sharded over the ranks, whose payload exchange is an RCCL all-gather ("gossip_round").
+
+A run without --full sets up, warms up, times --steps steps, writes the last step's outputs if
+--dump-outputs is given, and prints the result line: the headline figure only.  --full adds what
+else the default workload measures (both launch modes at --steps, stages, kernels, roofline, the
+plugin round, the CPU baseline, secondary / gossip_round / shard).
 
 Prints ONE JSON line (rank 0).
 """
@@ -76,14 +82,25 @@ def parse():
     p.add_argument("--repeats", type=int, default=0,
                    help="timed regions of exactly --steps steps each (0: auto, enough for a "
                         "stable median at small --steps); the line reports the median region")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline figure, everything else the default workload "
+                        "measures: both launch modes timed at --steps, per-stage and per-kernel "
+                        "times, the roofline object, the plugin round (product_one_node), the "
+                        "device copy rate, the CPU baseline (unless --no-cpu) and the secondary / "
+                        "gossip-round / shard objects (unless --no-extra).  Without it a run "
+                        "only sets up, warms up, times --steps steps and prints the result line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed "
+                        "(payload idx / val, the decoded model, the node's counter) as "
+                        "DIR/<name>.npy (dump_outputs)")
     return p.parse_args()
 
 
 def spawn_ranks(args):
     """``bench.py --gpus N`` (N > 1) started WITHOUT a launcher: run N ranks, one process per
     GPU, under torch.distributed.run as a child process and exit with its code.  This parent
-    never makes a HIP call (no GPU initialised before the ranks start); it times the CPU
-    baseline first (host cores only) and hands it to rank 0 through a file, so the ranks' GPU
+    never makes a HIP call (no GPU initialised before the ranks start); with --full it times the
+    CPU baseline first (host cores only) and hands it to rank 0 through a file, so the ranks' GPU
     work and the CPU sample never overlap."""
     import socket
     import subprocess
@@ -91,7 +108,7 @@ def spawn_ranks(args):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     path = None
-    if not args.no_cpu and args.workload == "c2":
+    if args.full and not args.no_cpu and args.workload == "c2":
         cpu = cpu_baseline(args.n, args.alpha, args.cpu_seconds)
         fd, path = tempfile.mkstemp(prefix="dpz_cpu_", suffix=".json")
         with os.fdopen(fd, "w") as f:
@@ -127,7 +144,37 @@ def timed_loop(fn, reps, stream):
 L3_BYTES = 256 * 2 ** 20  # MI355X Infinity Cache (MI355X_MICROARCH.md Â§ Infinity Cache)
 
 
-def gpu_case(n, alpha, dev, seed, steps, warmup, world, dist, rotate=None, streams=3, repeats=9):
+CAL_STEPS = 200  # a launch mode is chosen on regions of this many steps when --steps is larger
+
+
+def auto_repeats(steps, both_modes):
+    """Timed regions per launch mode: enough for a stable median at small --steps.  Where one
+    mode is timed at --steps (a run without --full at --steps > CAL_STEPS) the regions together
+    stay within max(--steps, 4000) steps, so a long run times --steps steps once."""
+    if both_modes:
+        return max(5, min(25, math.ceil(4000 / max(1, steps))))
+    return max(1, min(25, 4000 // max(1, steps)))
+
+
+def dump_outputs(path, d, limit=4_000_000, seed=20240229):
+    """``--dump-outputs``: what the last timed step computed, as a caller of the step receives it
+    (node state ``d``): its payload ``idx`` (float64, exact) and ``val``, the decoded model ``out``
+    and the node's ``counter`` (float32), one ``<name>.npy`` each.  An array of more than ``limit``
+    elements is written as a fixed sample of ``limit`` of them (seeded positions, ascending, the
+    same for every array of that length), so the files stay under 64 MB together."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, key, dt in (("idx", "idx", np.float64), ("val", "val", np.float32),
+                          ("decoded", "out", np.float32), ("counter", "counter", np.float32)):
+        t = d[key]
+        if t.numel() > limit:
+            pos = np.sort(np.random.default_rng(seed).integers(0, t.numel(), size=limit))
+            t = t[torch.from_numpy(pos).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(dt))
+
+
+def gpu_case(n, alpha, dev, seed, steps, warmup, world, dist, rotate=None, streams=3, repeats=9,
+             full=True, dump=None):
     """Time `steps` encode+decode steps.  Consecutive steps rotate over R independent node states
     (x, x0, counter, payload, output) so the timed working set is > 2x the 256 MiB Infinity
     Cache: every step streams its inputs from HBM, as a real round does after training.
@@ -143,7 +190,10 @@ def gpu_case(n, alpha, dev, seed, steps, warmup, world, dist, rotate=None, strea
     i % S, its own workspace), as decentralizepy runs procs_per_machine nodes per machine; the
     one-stream (one node) rate is measured beside it and the faster of the two is the line's
     value.  Every timed encode's sampled-path status is OR-ed into its workspace's sticky word
-    and checked after the loop (fell_back)."""
+    and checked after the loop (fell_back).  ``full=False`` returns after the timed regions
+    (no per-stage, per-kernel or plugin-round measurement) and, at steps > CAL_STEPS, times only
+    the launch mode that short regions of both show to be faster.  ``dump``: a directory for
+    dump_outputs, written right after the timed regions."""
     from decentralizepy_amd import codec
     from decentralizepy_amd._lib import DPZ_BATCH_DECODE, DPZ_BATCH_ENCODE, DPZ_BATCH_HINT
     k = round(alpha * n)
@@ -219,17 +269,40 @@ def gpu_case(n, alpha, dev, seed, steps, warmup, world, dist, rotate=None, strea
             t = float(tt.item())
         return t / count, t_host / count
 
-    def timed(batch, count):
-        """`repeats` timed regions of exactly `count` steps, each bracketed by barrier +
+    def timed(batch, count, regions, name):
+        """`regions` timed regions of exactly `count` steps, each bracketed by barrier +
         synchronize and max-over-ranks; the median region is the result (a 20-step region is
         under 1 ms of device time, so one host hiccup would otherwise move the line)."""
-        res = sorted(timed_once(batch, count) for _ in range(repeats))
-        spread.append([res[0][0], res[len(res) // 2][0], res[-1][0]])
+        res = sorted(timed_once(batch, count) for _ in range(regions))
+        spread[name] = [res[0][0], res[len(res) // 2][0], res[-1][0]]
         return res[len(res) // 2]
 
-    spread = []
-    s_multi, h_multi = timed(multi, steps)
-    s_serial, h_serial = timed(one, steps)
+    spread = {}
+    last = one  # the batch that runs the last timed region
+    calibrated = not full and S > 1 and steps > CAL_STEPS
+    if calibrated:
+        # both launch modes timed on short regions, then only the faster one at `steps`: a long
+        # run times `steps` steps once, not once per mode (--full times both at `steps`)
+        s_multi, h_multi = timed(multi, CAL_STEPS, 5, "multi_calibration")
+        s_serial, h_serial = timed(one, CAL_STEPS, 5, "serial_calibration")
+        if s_multi <= s_serial:  # (max over ranks: every rank takes the same mode)
+            s_multi, h_multi = timed(multi, steps, repeats, "multi")
+            s_serial, last = float("inf"), multi
+        else:
+            s_serial, h_serial = timed(one, steps, repeats, "serial")
+            s_multi = float("inf")
+    elif not full and S == 1:  # one stream: the one-node mode is the line's value
+        s_multi, h_multi = float("inf"), 0.0
+        s_serial, h_serial = timed(one, steps, repeats, "serial")
+    else:
+        s_multi, h_multi = timed(multi, steps, repeats, "multi")
+        s_serial, h_serial = timed(one, steps, repeats, "serial")
+    if dump is not None:
+        # the node state of the last timed step (the last region run: the one-node mode's, or
+        # the chosen mode's after a calibration); its ring was flushed inside the region, and
+        # holds the payload indices (with rings the encodes do not write the state's idx buffer)
+        j = (steps - 1) % R
+        dump_outputs(dump, dict(sets[j], idx=last.last_idx(j)))
     status = multi.sticky_status(clear=True) | one.sticky_status(clear=True)  # both loops
     fell_back = status != 0
     if dist is not None:
@@ -240,6 +313,15 @@ def gpu_case(n, alpha, dev, seed, steps, warmup, world, dist, rotate=None, strea
         s_step, s_host, mode = s_multi, h_multi, "multi"
     else:
         s_step, s_host, mode = s_serial, h_serial, "serial"
+    b_enc = 8 * n + 8 * k + 8 * k      # read x, x0; write idx, val; counter[idx] += 1 (r+w)
+    b_dec = 8 * n + 8 * k              # read local, payload; write out
+    res = dict(n=n, k=k, s_step=s_step, s_multi=s_multi, s_serial=s_serial, s_host=s_host,
+               mode=mode, streams=S, fell_back=fell_back, b_enc=b_enc, b_dec=b_dec, rotate=R,
+               repeats=repeats, calibrated=calibrated,
+               spread_ms={nm: [round(v * 1e3, 5) for v in sp] for nm, sp in spread.items()},
+               value=world * 4 * n / s_step / 2 ** 30)
+    if not full:
+        return res
     # per-stage device time with events on the one launch stream (encodes only, decodes only)
     stream = s_list[0]
     reps = max(2 * R, steps // 2)
@@ -264,18 +346,11 @@ def gpu_case(n, alpha, dev, seed, steps, warmup, world, dist, rotate=None, strea
                for name, (ms, c) in kt.result.items()}
     if "fold" in kernels:  # the standalone decode's launches are not part of the step
         kernels["fold"]["launches_per_step"] = 0.0 if fused_copy() else 1.0
-    b_enc = 8 * n + 8 * k + 8 * k      # read x, x0; write idx, val; counter[idx] += 1 (r+w)
-    b_dec = 8 * n + 8 * k              # read local, payload; write out
     fell_back |= (multi.sticky_status(clear=True) | one.sticky_status(clear=True)) != 0
     product = product_one_node(sets, n, k, stream, max(2 * R, min(steps, 200)), alpha=alpha)
     fell_back |= product["fell_back"]
-    return dict(n=n, k=k, s_step=s_step, s_multi=s_multi, s_serial=s_serial, s_host=s_host,
-                mode=mode, streams=S, fell_back=fell_back, t_enc=t_enc, t_dec=t_dec,
-                b_enc=b_enc, b_dec=b_dec, kernels=kernels, rotate=R, repeats=repeats,
-                product=product,
-                spread_ms={"multi": [round(v * 1e3, 5) for v in spread[0]],
-                           "serial": [round(v * 1e3, 5) for v in spread[1]]},
-                value=world * 4 * n / s_step / 2 ** 30)
+    res.update(fell_back=fell_back, t_enc=t_enc, t_dec=t_dec, kernels=kernels, product=product)
+    return res
 
 
 class _BenchMapping:
@@ -678,7 +753,7 @@ def main():
         dist = dist_mod
     dev = torch.device("cuda", local_rank)
     torch.cuda.set_device(dev)
-    repeats = args.repeats or max(5, min(25, math.ceil(4000 / max(1, args.steps))))
+    repeats = args.repeats or auto_repeats(args.steps, args.full or args.steps <= CAL_STEPS)
 
     if args.workload == "c4":
         rounds = max(3, min(args.steps, 20))
@@ -777,9 +852,12 @@ def main():
         _finish(dist)
         return
     r = gpu_case(args.n, args.alpha, dev, 1234 + rank, args.steps, args.warmup, world, dist,
-                 rotate=args.rotate, streams=args.streams, repeats=repeats)
+                 rotate=args.rotate, streams=args.streams, repeats=repeats, full=args.full,
+                 dump=args.dump_outputs if rank == 0 else None)
+    # everything beside the headline figure is measured with --full only
+    extras = args.full and not args.no_extra
     extra = None
-    if not args.no_extra:
+    if extras:
         # the other single-GPU size beside the headline (C2 when the headline is the 64 MiB
         # north-star tensor), every rank its own node's model (weak, like the headline)
         n2 = C2_N if args.n != C2_N else NORTH_STAR_N
@@ -808,7 +886,7 @@ def main():
     # sharded over the ranks and each round's payloads cross ranks in one RCCL all-gather, so a
     # multi-GPU run of this bench also times the collective path (strong scaling, 96 nodes fixed)
     gossip = shard_line = None
-    if not args.no_extra:
+    if extras:
         gossip = gossip_line(gossip_case(C2_N, 0.01, dev, rank, world, dist, rounds=5, warmup=2),
                              world)
         torch.cuda.empty_cache()
@@ -820,7 +898,7 @@ def main():
         torch.cuda.empty_cache()
 
     copy_gbs = None
-    if rank == 0:  # context: what a plain device-to-device copy reaches on this box
+    if rank == 0 and args.full:  # context: what a plain device-to-device copy reaches
         a = torch.empty(64 * 2 ** 20, dtype=torch.float32, device=dev)
         b = torch.empty_like(a)
         for _ in range(3):
@@ -830,7 +908,7 @@ def main():
         del a, b
 
     cpu = None
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         path = os.environ.get("DPZ_BENCH_CPU_BASELINE")
         if path and os.path.exists(path):  # timed by the spawning parent before the ranks
             with open(path) as f:
@@ -843,12 +921,6 @@ def main():
                 cpu["timed_by"] = "rank 0 after the GPU legs (the other ranks wait at a barrier)"
 
     if rank == 0:
-        t_enc, t_dec = r["t_enc"], r["t_dec"]
-        dec_gbs = r["b_dec"] / t_dec / 1e9
-        enc_gbs = r["b_enc"] / t_enc / 1e9
-        step_gbs = (r["b_enc"] + r["b_dec"]) / r["s_step"] / 1e9
-        serial_b = r["b_enc"] + r["b_dec"]
-        kern, dk, _ = kernel_table(r)
         line = {
             "metric": "GiB/s fp32 params encoded+decoded (device-resident), 1% top-k",
             "value": round(r["value"], 3),
@@ -884,10 +956,29 @@ def main():
                            "(filter writes the copy of x, select scatters the entries)"),
                 "rotated_states": r["rotate"],
                 "timing": (f"median of {r['repeats']} timed regions of exactly {args.steps} "
-                           f"steps (each: barrier + synchronize on both sides, max over ranks)"),
+                           f"steps (each: barrier + synchronize on both sides, max over ranks)"
+                           + (f"; the launch mode chosen on 5 regions of {CAL_STEPS} steps of "
+                              f"each mode before them" if r["calibrated"] else "")),
             },
             "spread_ms_per_step": r["spread_ms"],
-            "roofline": roofline_obj(dk, r["n"]),
+            "sampled_path_fell_back": r["fell_back"],
+        }
+        if args.full:
+            line.update(full_objects(r, copy_gbs))
+            line.update(cpu_baseline=cpu, secondary=extra, gossip_round=gossip, shard=shard_line)
+        print(json.dumps(line), flush=True)
+    _finish(dist)
+
+
+def full_objects(r, copy_gbs):
+    """The line's ``roofline`` and ``stages`` objects (--full) from gpu_case's result."""
+    t_enc, t_dec = r["t_enc"], r["t_dec"]
+    dec_gbs = r["b_dec"] / t_dec / 1e9
+    enc_gbs = r["b_enc"] / t_enc / 1e9
+    step_gbs = (r["b_enc"] + r["b_dec"]) / r["s_step"] / 1e9
+    serial_b = r["b_enc"] + r["b_dec"]
+    kern, dk, _ = kernel_table(r)
+    return {"roofline": roofline_obj(dk, r["n"]),
             "stages": {
                 "encode": {"avg_us": round(t_enc * 1e6, 3), "alg_bytes": r["b_enc"],
                            "GBps": round(enc_gbs, 1), "frac": round(enc_gbs / HBM_PEAK_GBS, 4),
@@ -902,14 +993,7 @@ def main():
                 "product_one_node": {k_: v for k_, v in r["product"].items() if k_ != "fell_back"},
                 "kernels": kern,
                 "torch_copy_GBps_256MiB": copy_gbs,
-            },
-            "cpu_baseline": cpu,
-            "secondary": extra,
-            "gossip_round": gossip,
-            "shard": shard_line,
-        }
-        print(json.dumps(line), flush=True)
-    _finish(dist)
+            }}
 
 
 def kernel_table(r):

@@ -456,6 +456,16 @@ class NodeStepBatch:
                 self._rings[j].commit(self.k)
                 self._last[j] = new[j]
 
+    def last_idx(self, j):
+        """Node j's payload indices as this batch encoded them last: its ``idx`` buffer, or with
+        ``rings`` the ring slot they were written into (a flush leaves the slot's content)."""
+        nodes = self._keep[0]
+        ring = self._rings[j].ring if self._rings is not None else None
+        if ring is None or self._last[j] == nodes[j]["idx"].data_ptr():
+            return nodes[j]["idx"]
+        off = (self._last[j] - ring.data_ptr()) // ring.element_size()
+        return ring[off:off + self.k]
+
     def sticky_status(self, clear=False):
         """OR of every encode's final status on these workspaces since the last clear."""
         v = 0

@@ -2,7 +2,8 @@
 # GPU-box session: parity tests, then (only if no crash) a short bench and a rocprofv3 summary.
 # Each GPU step has its own time limit; any abort/segfault/timeout ends the script.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}  # where this script writes its logs and results
+mkdir -p $OUT
 export TMPDIR=/tmp
 ok_or_stop() {  # rc 0 = pass, 1 = test failures (still safe to continue); anything else stops
   local rc=$1 what=$2
@@ -11,19 +12,19 @@ ok_or_stop() {  # rc 0 = pass, 1 = test failures (still safe to continue); anyth
 }
 STAGE=${1:-all}
 if [ "$STAGE" = all ] || [ "$STAGE" = test ]; then
-  timeout -k 10 ${TEST_TIMEOUT:-900} python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread ${PYTEST_ARGS} > gpurun_out/pytest_gpu.log 2>&1
+  timeout -k 10 ${TEST_TIMEOUT:-900} python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread ${PYTEST_ARGS} > $OUT/pytest_gpu.log 2>&1
   ok_or_stop $? pytest
-  tail -5 gpurun_out/pytest_gpu.log
+  tail -5 $OUT/pytest_gpu.log
 fi
 if [ "$STAGE" = all ] || [ "$STAGE" = bench ]; then
-  timeout -k 10 ${BENCH_TIMEOUT:-400} python bench.py ${BENCH_ARGS} > gpurun_out/bench.log 2>&1
+  timeout -k 10 ${BENCH_TIMEOUT:-400} python bench.py --full ${BENCH_ARGS} > $OUT/bench.log 2>&1
   ok_or_stop $? bench
-  tail -2 gpurun_out/bench.log
+  tail -2 $OUT/bench.log
 fi
 if [ "$STAGE" = all ] || [ "$STAGE" = prof ]; then
-  rm -rf gpurun_out/prof
-  timeout -k 10 ${PROF_TIMEOUT:-400} rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run -- python3 bench.py --steps 50 --warmup 10 --no-cpu --no-extra > gpurun_out/prof.log 2>&1
+  rm -rf $OUT/prof
+  timeout -k 10 ${PROF_TIMEOUT:-400} rocprofv3 --kernel-trace --stats -d $OUT/prof -o run -- python3 bench.py --full --steps 50 --warmup 10 --no-cpu --no-extra > $OUT/prof.log 2>&1
   ok_or_stop $? rocprof
-  find gpurun_out/prof -name '*kernel_stats*' | head -3
+  find $OUT/prof -name '*kernel_stats*' | head -3
 fi
 exit 0

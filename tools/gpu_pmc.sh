@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/pmc
 export TMPDIR=/tmp
-CMD="python3 bench.py --steps ${STEPS:-30} --warmup 5 --no-cpu --no-extra ${BENCH_ARGS}"
+CMD="python3 bench.py --full --steps ${STEPS:-30} --warmup 5 --no-cpu --no-extra ${BENCH_ARGS}"
 i=0
 while read -r group; do
   [ -z "$group" ] && continue
