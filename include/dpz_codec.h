@@ -568,6 +568,10 @@ int dpz_fpz_decode(const uint8_t* in, int64_t nbytes, int64_t n, int precision, 
 int64_t dpz_fft_workspace_bytes(int64_t n);
 /* 1 when dpz_rfft / dpz_irfft of n reals run the native kernels, 0 when they fall back to hipFFT. */
 int dpz_fft_native(int64_t n);
+/* Alignment: the kernels address complex data as 8-byte (re, im) pairs, and for even n the real
+ * vector as n / 2 such pairs.  The complex pointer (dpz_rfft's out, dpz_irfft's coeffs) must be
+ * 8-byte aligned for every n, the real pointer (x / out) for every even n that runs the native
+ * kernels; otherwise DPZ_ERR_ARG is returned before anything is launched.                        */
 /* out[m complex] = rfft(x[n]).  Asynchronous on stream.                                          */
 int dpz_rfft(const float* x, int64_t n, float* out, void* ws, size_t ws_bytes, dpz_stream_t stream);
 /* out[n] = irfft(coeffs[m complex], n) with torch's "backward" normalisation (1/n).  coeffs may be
