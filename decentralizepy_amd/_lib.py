@@ -143,6 +143,12 @@ SIGNATURES = {
                                         _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                         _i64, _c_void_p, _c_void_p, _size, _c_void_p, _size,
                                         _int, _c_void_p]),
+    "dpz_encode_replace_batch_ws": (_int, [_int, _int, _c_void_p, _c_void_p, _i64, _i64,
+                                           _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                           _c_void_p, _i64, _c_void_p, _c_void_p, _size,
+                                           _c_void_p, _size, _int, _c_void_p, _c_void_p,
+                                           ctypes.POINTER(ctypes.c_uint32),
+                                           ctypes.POINTER(_int)]),
     "dpz_topk_sticky_status": (_int, [_c_void_p, _size, _int, ctypes.POINTER(ctypes.c_int32),
                                       _c_void_p]),
     "dpz_elias_max_bytes": (_i64, [_i64]),

@@ -357,7 +357,14 @@ class NodeStepBatch:
     reference's deserialized_model starts from the receiver's state_dict, PartialModel.py:278-295;
     with ``decode_src(j) != j`` the encoder's filter writes the copy of ``x``), on
     ``streams[j % len(streams)]`` with that stream's workspace.  The pointer arrays are built
-    once; :meth:`run` is one ctypes call whatever m is (the host loop is native)."""
+    once; :meth:`run` is one ctypes call whatever m is (the host loop is native).  Where every
+    step of a run is the fused step (a neighbour's payload over the model being encoded, sampled
+    path), the steps of a stream are pipelined (dpz_encode_replace_batch_ws): they rotate
+    through the stream's workspace and two internal ones (``pipe_workspaces``), and a step's
+    selection tail rides in the next steps' filter launches; ``pipelined`` holds the number of
+    steps of the last run that took that schedule.  Which encode every workspace last held is
+    recorded on the host, so a step takes the prior window (DPZ_BATCH_HINT) only where its
+    workspace holds one."""
 
     def __init__(self, nodes, n, k, streams, workspaces, decode_src=None, rings=None):
         """``rings``: one :class:`~decentralizepy_amd._device.RingCounter` per node (over its
@@ -401,7 +408,15 @@ class NodeStepBatch:
         self._streams = Q(*[s.cuda_stream for s in streams])
         self._S = S
         self.workspaces = workspaces
-        self._keep = (nodes, wbufs, dbufs, streams)
+        # the pipelined schedule (dpz_encode_replace_batch_ws): two more workspaces per stream,
+        # and the host record of which encode every workspace last held (the hint bookkeeping)
+        self.pipe_workspaces = [Workspace(workspaces[0].device) for _ in range(2 * S)]
+        pbufs = [w.get(n, k) for w in self.pipe_workspaces]
+        self._ws_pipe = (ctypes.c_void_p * (2 * S))(*[b.data_ptr() for b in pbufs])
+        self._ws_bytes = min([self._ws_bytes] + [b.numel() for b in pbufs])
+        self._ws_sig = (ctypes.c_uint32 * (3 * S))()
+        self.pipelined = 0  # steps of the last run that took the pipelined schedule
+        self._keep = (nodes, wbufs, dbufs, streams, pbufs)
         self._rings = rings
         if rings is not None:
             if len(rings) != m:
@@ -446,11 +461,14 @@ class NodeStepBatch:
             # a payload encoded earlier in this run (src < j, same stream) is the new slot
             ri = P(*([(new[q] if (enc and q < j) else self._last[q])
                       for j, q in ((j, self._src[j]) for j in range(m))] + [0] * (self.m - m)))
-        rc = _lib.lib().dpz_encode_replace_batch(
+        piped = ctypes.c_int(0)
+        rc = _lib.lib().dpz_encode_replace_batch_ws(
             m, int(what), self._x, self._x0, self.n, self.k, self._cnt, idx, self._val,
             self._rl, ri, self._rv, self.k, self._ro, self._ws, self._ws_bytes, self._dws,
-            self._dws_bytes, self._S, self._streams)
-        check(rc, "dpz_encode_replace_batch")
+            self._dws_bytes, self._S, self._streams, self._ws_pipe, self._ws_sig,
+            ctypes.byref(piped))
+        check(rc, "dpz_encode_replace_batch_ws")
+        self.pipelined = int(piped.value)
         if self._rings is not None and enc:
             for j in range(m):
                 self._rings[j].commit(self.k)
@@ -469,7 +487,7 @@ class NodeStepBatch:
     def sticky_status(self, clear=False):
         """OR of every encode's final status on these workspaces since the last clear."""
         v = 0
-        for w in self.workspaces:
+        for w in list(self.workspaces) + self.pipe_workspaces:
             v |= topk_sticky_status(w, clear)
         return v
 

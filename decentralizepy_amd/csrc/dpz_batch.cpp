@@ -7,6 +7,7 @@
 // node j goes to stream j % n_streams (one workspace per stream), and its sampled-path status
 // word is copied to status[j] (device) on the same stream so the caller reads all of them once.
 #include <cstdlib>
+#include <vector>
 #include <hip/hip_runtime.h>
 
 #include "../../include/dpz_codec.h"
@@ -104,14 +105,58 @@ extern "C" int dpz_decode_average_batch_guarded(int m, const float* const* local
 // One codec step per node: encode node j's model (as dpz_topk_encode_batch) and/or replace-decode
 // the payload (r_idx[j], r_val[j]) into r_out[j] from r_local[j] (dpz_decode_average with
 // DPZ_FOLD_REPLACE_ONLY), node j on streams[j % n_streams].  Host cost: the launches only.
-extern "C" int dpz_encode_replace_batch(int m, int what, const float* const* x,
-                                        const float* const* x0, int64_t n, int64_t k,
-                                        int32_t* const* counter, int32_t* const* idx_out,
-                                        float* const* val_out, const float* const* r_local,
-                                        const int32_t* const* r_idx, const float* const* r_val,
-                                        int64_t r_k, float* const* r_out, void* const* ws,
-                                        size_t ws_bytes, void* const* dws, size_t dws_bytes,
-                                        int n_streams, const dpz_stream_t* streams) {
+static bool ranges_overlap(const void* p, size_t pb, const void* q, size_t qb) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  return a < b + qb && b < a + pb;
+}
+
+// The pipelined schedule (dpz_topk_sampled.hip topk_pipe_chain) applies to a call whose every
+// step is today's fused encode + replace (both operations, a neighbour's payload decoded over
+// the model being encoded) on the sampled path with aligned operands, and whose payloads come
+// from an earlier call or from a step of the same stream (its compact then sits in another
+// launch than the scatter that reads it).  Anything else keeps the plain enqueue.
+static bool pipe_applies(int m, int what, const float* const* x, const float* const* x0,
+                         int64_t n, int64_t k, int32_t* const* idx_out, float* const* val_out,
+                         const float* const* r_local, const int32_t* const* r_idx,
+                         const float* const* r_val, int64_t r_k, float* const* r_out,
+                         size_t ws_bytes, int n_streams) {
+  if (m < 1 || !(what & DPZ_BATCH_ENCODE) || !(what & DPZ_BATCH_DECODE) || !x0) return false;
+  if (!dpz::topk_pipe_ok(n, k, ws_bytes) || r_k < 1 || r_k > n) return false;
+  const size_t nb = (size_t)n * 4, kb = (size_t)k * 4;
+  for (int j = 0; j < m; ++j) {
+    if (!x[j] || !x0[j] || !idx_out[j] || !val_out[j] || !r_idx[j] || !r_val[j] || !r_out[j])
+      return false;
+    if (r_local[j] != x[j] || r_idx[j] == idx_out[j] || r_val[j] == val_out[j]) return false;
+    if (!dpz::aligned16(x[j]) || !dpz::aligned16(x0[j]) || !dpz::aligned16(r_out[j])) return false;
+    if (ranges_overlap(r_out[j], nb, x[j], nb) || ranges_overlap(r_out[j], nb, x0[j], nb) ||
+        ranges_overlap(r_out[j], nb, idx_out[j], kb) || ranges_overlap(r_out[j], nb, val_out[j], kb))
+      return false;
+    for (int i = 0; i < m; ++i) {
+      if (i == j) continue;
+      // three steps of a stream are in flight at once: no two steps of a call share a buffer
+      if (x[i] == x[j] || r_out[i] == r_out[j] || idx_out[i] == idx_out[j] ||
+          val_out[i] == val_out[j])
+        return false;
+      // the payload's producer, an earlier or a later step of this call (the payload is then its
+      // previous one): on the same stream its compact is two launches after its filter, like the
+      // scatter that reads the payload, so the two never share a launch
+      if ((idx_out[i] == r_idx[j] || val_out[i] == r_val[j]) && i % n_streams != j % n_streams)
+        return false;
+    }
+  }
+  return true;
+}
+
+static int encode_replace_batch(int m, int what, const float* const* x,
+                                const float* const* x0, int64_t n, int64_t k,
+                                int32_t* const* counter, int32_t* const* idx_out,
+                                float* const* val_out, const float* const* r_local,
+                                const int32_t* const* r_idx, const float* const* r_val,
+                                int64_t r_k, float* const* r_out, void* const* ws,
+                                size_t ws_bytes, void* const* dws, size_t dws_bytes,
+                                int n_streams, const dpz_stream_t* streams, void* const* ws_pipe,
+                                uint32_t* ws_sig, int* pipelined) {
+  if (pipelined) *pipelined = 0;
   if (m < 0 || n_streams < 1 || !streams || !(what & (DPZ_BATCH_ENCODE | DPZ_BATCH_DECODE)) ||
       (what & ~(DPZ_BATCH_ENCODE | DPZ_BATCH_DECODE | DPZ_BATCH_HINT | DPZ_BATCH_HINT_ALL)))
     return DPZ_ERR_ARG;
@@ -130,11 +175,51 @@ extern "C" int dpz_encode_replace_batch(int m, int what, const float* const* x,
   // DPZ_BATCH_COSCHED=0 / 1 forces the plain / co-scheduled enqueue (diagnostic build, A/B)
   const int cs_env = (int)DPZ_KNOB_INT(BATCH_COSCHED, -1);
   const bool cosched = cs_env >= 0 ? cs_env != 0 : n_streams == 1;
+  const bool want_hint = (what & (DPZ_BATCH_HINT | DPZ_BATCH_HINT_ALL)) != 0;
+  // DPZ_BATCH_PIPE (diagnostic build, A/B): 0 = the plain enqueue, 1 = only the compact rides in
+  // the next step's filter launch (the select stays a launch of its own), 2 = the whole tail
+  const int pipe_mode = (int)DPZ_KNOB_INT(BATCH_PIPE, 2);
+  if (pipe_mode > 0 && cs_env != 0 && ws_pipe && ws_sig &&
+      pipe_applies(m, what, x, x0, n, k, idx_out, val_out, r_local, r_idx, r_val, r_k, r_out,
+                   ws_bytes, n_streams)) {
+    // the chain of stream q: steps q, q + S, ..; step i of it works in workspace i % 3 — the
+    // caller's ws[q], then the stream's two extra ones — restarting at ws[q] on every call.
+    // A step is hinted only where its workspace has completed an encode of this signature
+    // (ws_sig, kept by the caller across calls): an unprimed workspace gets its sample launch,
+    // never a device-side miss
+    const uint32_t sig = dpz::hint_signature(n, k, true, DPZ_ACC_NONE, true);
+    std::vector<dpz::PipeStep> chain;
+    for (int q = 0; q < n_streams && q < m; ++q) {
+      if (!ws[q] || !ws_pipe[2 * q] || !ws_pipe[2 * q + 1]) return DPZ_ERR_ARG;
+      chain.clear();
+      for (int j = q, i = 0; j < m; j += n_streams, ++i) {
+        const int r = i % 3;
+        void* w = r == 0 ? ws[q] : ws_pipe[2 * q + r - 1];
+        const bool hint = want_hint && ws_sig[3 * q + r] == sig;
+        ws_sig[3 * q + r] = sig;
+        chain.push_back(dpz::PipeStep{x[j], x0[j], counter ? counter[j] : nullptr, idx_out[j],
+                                      val_out[j], r_idx[j], r_val[j], r_out[j],
+                                      static_cast<char*>(w), hint});
+      }
+      int rc = dpz::topk_pipe_chain((int)chain.size(), chain.data(), n, k, r_k, pipe_mode,
+                                    static_cast<hipStream_t>(streams[q]));
+      if (rc != DPZ_OK) return rc;
+    }
+    if (pipelined) *pipelined = m;
+    return DPZ_OK;
+  }
   for (int j = 0; j < m; ++j) {
     const int q = j % n_streams;
-    // the prior window: every encode with HINT_ALL, all but each stream's first with HINT
-    const int hint = ((what & DPZ_BATCH_HINT_ALL) || ((what & DPZ_BATCH_HINT) && j >= n_streams))
-                         ? DPZ_TOPK_HINT : 0;
+    // the prior window: every encode with HINT_ALL, all but each stream's first with HINT; with
+    // the caller's record of the workspaces (ws_sig), where ws[q] holds an encode of this signature
+    int hint = ((what & DPZ_BATCH_HINT_ALL) || ((what & DPZ_BATCH_HINT) && j >= n_streams))
+                   ? DPZ_TOPK_HINT : 0;
+    if (ws_sig && (what & DPZ_BATCH_ENCODE) && dpz::use_sampled(n, k)) {
+      const uint32_t sig =
+          dpz::hint_signature(n, k, n_streams > 1, DPZ_ACC_NONE, x0 && x0[j] != nullptr);
+      hint = (want_hint && ws_sig[3 * q] == sig) ? DPZ_TOPK_HINT : 0;
+      ws_sig[3 * q] = sig;
+    }
     const bool both = (what & DPZ_BATCH_ENCODE) && (what & DPZ_BATCH_DECODE) &&
                       r_idx[j] != idx_out[j] && r_val[j] != val_out[j];
     const bool fused = both && r_local[j] == x[j] && cs_env != 0;
@@ -165,4 +250,33 @@ extern "C" int dpz_encode_replace_batch(int m, int what, const float* const* x,
     }
   }
   return DPZ_OK;
+}
+
+extern "C" int dpz_encode_replace_batch(int m, int what, const float* const* x,
+                                        const float* const* x0, int64_t n, int64_t k,
+                                        int32_t* const* counter, int32_t* const* idx_out,
+                                        float* const* val_out, const float* const* r_local,
+                                        const int32_t* const* r_idx, const float* const* r_val,
+                                        int64_t r_k, float* const* r_out, void* const* ws,
+                                        size_t ws_bytes, void* const* dws, size_t dws_bytes,
+                                        int n_streams, const dpz_stream_t* streams) {
+  return encode_replace_batch(m, what, x, x0, n, k, counter, idx_out, val_out, r_local, r_idx,
+                              r_val, r_k, r_out, ws, ws_bytes, dws, dws_bytes, n_streams, streams,
+                              nullptr, nullptr, nullptr);
+}
+
+extern "C" int dpz_encode_replace_batch_ws(int m, int what, const float* const* x,
+                                           const float* const* x0, int64_t n, int64_t k,
+                                           int32_t* const* counter, int32_t* const* idx_out,
+                                           float* const* val_out, const float* const* r_local,
+                                           const int32_t* const* r_idx,
+                                           const float* const* r_val, int64_t r_k,
+                                           float* const* r_out, void* const* ws, size_t ws_bytes,
+                                           void* const* dws, size_t dws_bytes, int n_streams,
+                                           const dpz_stream_t* streams, void* const* ws_pipe,
+                                           uint32_t* ws_sig, int* pipelined) {
+  if (!ws_pipe || !ws_sig) return DPZ_ERR_ARG;
+  return encode_replace_batch(m, what, x, x0, n, k, counter, idx_out, val_out, r_local, r_idx,
+                              r_val, r_k, r_out, ws, ws_bytes, dws, dws_bytes, n_streams, streams,
+                              ws_pipe, ws_sig, pipelined);
 }

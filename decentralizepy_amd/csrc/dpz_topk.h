@@ -343,6 +343,28 @@ int topk_encode_status(const float* x, const float* x0, float* acc, int acc_mode
 // dpz_topk_encode_nodes (dpz_topk_sampled.hip): m nodes' encodes, one launch per phase
 int topk_encode_nodes(int m, const void* table, int64_t n, int64_t k, size_t ws_bytes, int flags,
                       hipStream_t st);
+// One step of a pipelined chain (dpz_topk_sampled.hip topk_pipe_chain): the fused encode +
+// replace decode of one node, out = x with the payload (r_idx, r_val) scattered in; ws is the
+// workspace the step works in (chain position % 3), hint: it holds a completed encode of this
+// signature (n, k, shared grid), so the filter takes its window from it and no sample launch runs
+struct PipeStep {
+  const float* x;
+  const float* x0;
+  int32_t* counter;
+  int32_t* idx_out;
+  float* val_out;
+  const int32_t* r_idx;
+  const float* r_val;
+  float* r_out;
+  char* ws;
+  bool hint;
+};
+// n, k, workspace size fit the pipelined schedule (sampled path, sparse alpha, <= 4096 segments)
+bool topk_pipe_ok(int64_t n, int64_t k, size_t ws_bytes);
+// p consecutive steps of one stream: launch i = filter(c_i) + select(c_{i-1}) + compact(c_{i-2})
+// (mode 2), or filter(c_i) + compact(c_{i-1}) with the select as its own launch (mode 1)
+int topk_pipe_chain(int p, const PipeStep* c, int64_t n, int64_t k, int64_t r_k, int mode,
+                    hipStream_t st);
 static inline bool use_sampled(int64_t n, int64_t k) {
   return n >= (1 << 18) && k >= 1 && k <= n / 2;
 }

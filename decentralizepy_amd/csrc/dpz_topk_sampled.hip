@@ -639,10 +639,17 @@ __device__ __forceinline__ bool wave_bstar(const uint32_t* gh, uint32_t above, u
 // finds the threshold bin b* (wave 0), counts each filter block's candidates above b*
 // (blkabove) and appends the bin-b* entries, staged in LDS, to sub-list (block % 16) with one
 // atomic per block.
-template <bool VEC>
+// NT = 256 (the pipelined step batch's merged launch, pipe_step_kernel): 4 waves x 2 wave
+// segments per block, four fine bins per thread for the histogram sum; four blocks stand for one
+// 1024-thread block (the same blkabove zero padding), still one atomic per block onto sub-list
+// block % 16 (W = 8192: 1024 blocks, 64 arrivals per counter).
+template <bool VEC, int NT = 1024>
 __device__ __forceinline__ void sampled_select_kernel_body(KeySrc s, int64_t n, int64_t k, int64_t W, int64_t B, int64_t R, int64_t CAP, TopkCtrl* ctrl, const uint32_t* __restrict__ ghist, const uint32_t* __restrict__ segcnt, const uint32_t* __restrict__ cidx, const uint32_t* __restrict__ ckey, uint32_t* blkabove, uint32_t* blcnt, uint32_t* blkey, uint32_t* blidx, ReplaceJob pj, const uint32_t BID) {
+  static_assert(NT == 1024 || NT == 256, "select block: 1024 or 256 threads");
+  constexpr int SS = NT / 64 * 2;  // wave segments per block
+  constexpr int NQ = HB / NT;      // fine bins per thread
   {
-    const int64_t own = (W + SEL_SEGS - 1) / SEL_SEGS;
+    const int64_t own = ((W + SEL_SEGS - 1) / SEL_SEGS) * (SEL_SEGS / SS);
     if ((int64_t)BID >= own) {  // co-scheduled replace decode
       replace_block(pj, (int64_t)BID - own);
       return;
@@ -651,11 +658,11 @@ __device__ __forceinline__ void sampled_select_kernel_body(KeySrc s, int64_t n, 
   STAMP_MIN(6);
   STAMP_T0(8);
   __shared__ __attribute__((aligned(16))) uint32_t gh[GH_STRIDE];
-  __shared__ uint32_t fbabove[SEL_SEGS / 4];
+  __shared__ uint32_t fbabove[SS / 4];
   __shared__ uint32_t lkey[SEL_LCAP], lidx[SEL_LCAP];
   __shared__ uint32_t lcnt, gbase, sb_bstar, sb_need, sb_ok;
   const int t = threadIdx.x, wid = t >> 6, lane = t & 63;
-  const int64_t seg0 = (int64_t)BID * SEL_SEGS + wid * 2;
+  const int64_t seg0 = (int64_t)BID * SS + wid * 2;
   const uint32_t cnt0 = seg0 < W ? segcnt[seg0] : 0u;
   const uint32_t cnt1 = seg0 + 1 < W ? segcnt[seg0 + 1] : 0u;
   // the first 64 entries of both lists are loaded with the counts and the histogram, not after
@@ -674,11 +681,12 @@ __device__ __forceinline__ void sampled_select_kernel_body(KeySrc s, int64_t n, 
   const uint32_t fstatus = ctrl->status;
   // histogram copies (bins t and, for t == 0, the above-window bin HB), then chunks 1 .. PFS-1
   // of segments with more than 64 candidates — all loads issued before any sum is formed
-  static_assert(HB == 1024, "select: one fine bin per thread + the above-window bin");
-  uint32_t v[GH_COPIES], va[GH_COPIES];
+  static_assert(HB == 1024, "select: NQ fine bins per thread + the above-window bin");
+  uint32_t v[GH_COPIES][NQ], va[GH_COPIES];
 #pragma unroll
   for (int c = 0; c < GH_COPIES; ++c) {
-    v[c] = ghist[c * GH_STRIDE + t];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) v[c][q] = ghist[c * GH_STRIDE + q * NT + t];
     va[c] = t == 0 ? ghist[c * GH_STRIDE + HB] : 0u;
   }
 #pragma unroll
@@ -698,17 +706,20 @@ __device__ __forceinline__ void sampled_select_kernel_body(KeySrc s, int64_t n, 
   }
   if (fstatus) return;  // uniform over the grid
   {
-    uint32_t sum = 0, suma = 0;
+    uint32_t suma = 0;
 #pragma unroll
-    for (int c = 0; c < GH_COPIES; ++c) {
-      sum += v[c];
-      suma += va[c];
+    for (int c = 0; c < GH_COPIES; ++c) suma += va[c];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      uint32_t sum = 0;
+#pragma unroll
+      for (int c = 0; c < GH_COPIES; ++c) sum += v[c][q];
+      gh[q * NT + t] = sum;
     }
-    gh[t] = sum;
     if (t == 0) gh[HB] = suma;
   }
   STAMP_T0(12);
-  if (t < SEL_SEGS / 4) fbabove[t] = 0;
+  if (t < SS / 4) fbabove[t] = 0;
   if (t == 0) lcnt = 0;
   __syncthreads();
   if (wid == 0) {
@@ -800,8 +811,8 @@ __device__ __forceinline__ void sampled_select_kernel_body(KeySrc s, int64_t n, 
     if (lane == 0 && above) atomicAdd(&fbabove[(wid * 2 + u) >> 2], above);
   }
   __syncthreads();
-  if (t < SEL_SEGS / 4) {
-    const int64_t fb = (int64_t)BID * (SEL_SEGS / 4) + t;
+  if (t < SS / 4) {
+    const int64_t fb = (int64_t)BID * (SS / 4) + t;
     blkabove[fb] = fb < B ? fbabove[t] : 0u;  // zero-padded to a multiple of 8 (compact)
   }
   STAMP_T0(10);
@@ -811,7 +822,7 @@ __device__ __forceinline__ void sampled_select_kernel_body(KeySrc s, int64_t n, 
     if (t == 0) gbase = atomicAdd(&blcnt[sub], nl > SEL_LCAP ? (uint32_t)BCAP : nl);
     __syncthreads();
     const uint32_t gb = gbase;
-    for (uint32_t j = t; j < nl && j < SEL_LCAP; j += 1024) {
+    for (uint32_t j = t; j < nl && j < SEL_LCAP; j += NT) {
       const uint32_t p = gb + j;
       if (p < SUBCAP) {
         blkey[sub * SUBCAP + p] = lkey[j];
@@ -1668,7 +1679,7 @@ struct WsOff {
 };
 
 template <class T>
-__device__ __forceinline__ T* wsp(char* ws, uint64_t off) {
+__host__ __device__ __forceinline__ T* wsp(char* ws, uint64_t off) {
   return reinterpret_cast<T*>(ws + off);
 }
 
@@ -1783,6 +1794,218 @@ int topk_encode_nodes(int m, const void* table, int64_t n, int64_t k, size_t ws_
   else
     DPZ_TIMED(DPZ_KT_TOPK_COMPACT, st, (nodes_compact_kernel<false, false><<<(unsigned)(m * ncb), 256, 0, st>>>(
         tab, o, n, k, g.W, g.R, g.CAP, ncb, mask_words(n), sig)));
+  return DPZ_OK;
+}
+
+// ---- the pipelined step batch (dpz_encode_replace_batch_ws, dpz_batch.cpp) ---------------------
+// Consecutive steps c_0 .. c_{p-1} of one stream encode different node states, and step c_i works
+// in workspace i % 3: launch i carries the filter of c_i (with its fused copy out = x), the select
+// of c_{i-1} and the compact of c_{i-2} with that step's scatter blocks, each part in blocks of its
+// own, so the latency-bound tail of a step runs beside the next steps' streaming.  Every
+// dependency (select after filter, compact after select, scatter after the filter's copy and after
+// the payload's compact) is a launch boundary: no block waits for another block of its launch, and
+// the block order (topk_pipe_chain) is for speed only.
+// The parts' pointers, gathered on the host; the kernel takes each as an argument of its own: read
+// out of a by-value struct argument they are generic-address pointers to the compiler, and the
+// compact part then spilled (128 VGPRs + 264 bytes of scratch per lane against 92 VGPRs and none).
+struct PipeFilterPart {
+  const float* x;
+  const float* x0;
+  TopkCtrl* ctrl;
+  const uint32_t* chist;
+  uint32_t* ghist;
+  uint32_t* segcnt;
+  uint32_t* cidx;
+  uint32_t* ckey;
+  float* cval;
+  uint32_t* blcnt;
+  float* out;      // the fused copy
+  uint32_t hsig;   // the step's prior-window signature, 0 = a sample launch ran
+};
+struct PipeSelectPart {
+  const float* x;
+  const float* x0;
+  TopkCtrl* ctrl;
+  const uint32_t* ghist;
+  const uint32_t* segcnt;
+  const uint32_t* cidx;
+  const uint32_t* ckey;
+  uint32_t* blkabove;
+  uint32_t* blcnt;
+  uint32_t* blkey;
+  uint32_t* blidx;
+};
+struct PipeCompactPart {
+  const float* x;
+  const float* x0;
+  TopkCtrl* ctrl;
+  uint32_t* chist;
+  const uint32_t* blkabove;
+  const uint32_t* blcnt;
+  const uint32_t* blkey;
+  const uint32_t* blidx;
+  const uint32_t* segcnt;
+  const uint32_t* cidx;
+  const uint32_t* ckey;
+  const float* cval;
+  uint32_t* ghist;
+  int32_t* idx_out;
+  float* val_out;
+  int32_t* counter;
+  ReplaceJob pj;   // the step's received payload, scattered into its out
+};
+
+// grid: the nf filter blocks, then nc compact + scatter blocks, then nsel select blocks; with
+// nf == 0 the filter's blocks (if any) come after the tail's
+__global__ void __launch_bounds__(256, 4) pipe_step_kernel(
+    KeySrc fs, TopkCtrl* f_ctrl, const uint32_t* __restrict__ f_chist, uint32_t* f_ghist,
+    uint32_t* f_segcnt, uint32_t* f_cidx, uint32_t* f_ckey, float* f_cval, uint32_t* f_blcnt,
+    float* __restrict__ f_out, uint32_t f_hsig,
+    KeySrc ss, TopkCtrl* s_ctrl, const uint32_t* __restrict__ s_ghist,
+    const uint32_t* __restrict__ s_segcnt, const uint32_t* __restrict__ s_cidx,
+    const uint32_t* __restrict__ s_ckey, uint32_t* s_blkabove, uint32_t* s_blcnt,
+    uint32_t* s_blkey, uint32_t* s_blidx,
+    KeySrc cs, TopkCtrl* c_ctrl, uint32_t* c_chist, const uint32_t* __restrict__ c_blkabove,
+    const uint32_t* __restrict__ c_blcnt, const uint32_t* __restrict__ c_blkey,
+    const uint32_t* __restrict__ c_blidx, const uint32_t* __restrict__ c_segcnt,
+    const uint32_t* __restrict__ c_cidx, const uint32_t* __restrict__ c_ckey,
+    const float* __restrict__ c_cval, uint32_t* c_ghist, int32_t* c_idx_out, float* c_val_out,
+    int32_t* c_counter, ReplaceJob c_pj,
+    int64_t n, int64_t k, uint32_t r_lo, uint32_t r_hi, int64_t W, int64_t B, int64_t R,
+    int64_t CAP, uint32_t nc, uint32_t nsel, uint32_t nf, uint32_t sig) {
+  uint32_t bid = blockIdx.x;
+  // nf != 0: the nf filter blocks hold the lowest indices, then the tail's (filter first)
+  if (nf) {
+    if (bid < nf) {
+      sampled_filter_pipe_kernel_body<1, 1, 4, 4, true>(
+          fs, n, r_lo, r_hi, W, R, CAP, f_ctrl, f_chist, f_ghist, f_segcnt, f_cidx, f_ckey, f_cval,
+          f_out, FoldBase{}, f_hsig, f_blcnt, 0, bid);
+      return;
+    }
+    bid -= nf;
+  }
+  if (bid < nc) {
+    sampled_compact_kernel_body<true, false, 2, false>(
+        cs, n, k, W, R, CAP, c_ctrl, c_chist, c_blkabove, c_blcnt, c_blkey, c_blidx, c_segcnt,
+        c_cidx, c_ckey, c_cval, cs.x, c_idx_out, c_val_out, c_counter, nullptr, nullptr, c_pj, 0,
+        0, nullptr, nullptr, 0, c_ghist, sig, bid);
+    return;
+  }
+  bid -= nc;
+  if (bid < nsel) {
+    sampled_select_kernel_body<true, 256>(ss, n, k, W, B, R, CAP, s_ctrl, s_ghist, s_segcnt,
+                                          s_cidx, s_ckey, s_blkabove, s_blcnt, s_blkey, s_blidx,
+                                          ReplaceJob{}, bid);
+    return;
+  }
+  bid -= nsel;
+  if (nf) return;
+  sampled_filter_pipe_kernel_body<1, 1, 4, 4, true>(fs, n, r_lo, r_hi, W, R, CAP, f_ctrl, f_chist,
+                                                    f_ghist, f_segcnt, f_cidx, f_ckey, f_cval,
+                                                    f_out, FoldBase{}, f_hsig, f_blcnt, 0, bid);
+}
+
+bool topk_pipe_ok(int64_t n, int64_t k, size_t ws_bytes) {
+  // the sampled path with the scattered-atomic counter form (sparse alpha) at the shared-grid
+  // geometry: at most 4096 segments, so the filter part runs at depth 4 with 4 waves per SIMD
+  // and leaves wave slots to the tail's blocks
+  if (n <= 0 || n >= (int64_t(1) << 31) || !use_sampled(n, k) || k > n / 32) return false;
+  if (ws_bytes < ws_bytes_needed(n, k)) return false;
+  return fast_geom(n, k, true).W <= 4096 && DPZ_KNOB_INT(FILTER_PIPE, 1) > 0;
+}
+
+int topk_pipe_chain(int p, const PipeStep* c, int64_t n, int64_t k, int64_t r_k, int mode,
+                    hipStream_t st) {
+  if (p < 1 || !c || !topk_pipe_ok(n, k, ws_bytes_needed(n, k)) || r_k < 1 || r_k > n)
+    return DPZ_ERR_ARG;
+  const WsLayout L = ws_layout(n, k, true);
+  const FastGeom& g = L.fg;
+  const WsOff o{L.ctrl, L.chist, L.f_ghist, L.f_segcnt, L.f_blkabove, L.f_cidx, L.f_ckey,
+                L.f_cval, L.f_blcnt, L.f_blkey, L.f_blidx};
+  const uint32_t sig = hint_signature(n, k, true, DPZ_ACC_NONE, true);
+  const int nsb = SMP_NCHUNK / 16;  // 256-thread sample blocks
+  const uint32_t nb = (uint32_t)g.B;
+  const uint32_t nsel1024 = (uint32_t)((g.W + SEL_SEGS - 1) / SEL_SEGS);
+  const uint32_t nsel256 = nsel1024 * 4;
+  const uint32_t ncb = (uint32_t)((g.W + 7) / 8);                   // compact's own blocks
+  const uint32_t nsc = (uint32_t)((scatter_chunks(r_k) + 3) / 4);   // scatter blocks (4 chunks each)
+  uint32_t r_lo, r_hi;
+  window_ranks(n, k, &r_lo, &r_hi);
+  const bool full = mode >= 2;
+  // The filter's blocks hold the lowest indices: at 4 blocks per CU (38.8 KB of LDS each) the
+  // tail's ~1400 blocks of a 64 MiB step, dispatched first, took every slot and the filter waited
+  // for them (one-node step 54.8 us; filter first 50.3 us, 60.4 us unpipelined, MI355X, DESIGN.md
+  // §3.9).  DPZ_PIPE_ORDER=0 (diagnostic build, A/B): the tail's blocks first
+  const bool ffirst = DPZ_KNOB_INT(PIPE_ORDER, 1) != 0;
+  // the last launch carries the compact of c_{p-1}: launch p + 1 (full), launch p (compact only)
+  const int last = full ? p + 1 : p;
+  for (int i = 0; i <= last; ++i) {
+    const PipeStep* fs = i < p ? &c[i] : nullptr;
+    const PipeStep* ss = (full && i >= 1 && i <= p) ? &c[i - 1] : nullptr;
+    const int ci = full ? i - 2 : i - 1;
+    const PipeStep* cs = (ci >= 0 && ci < p) ? &c[ci] : nullptr;
+    PipeFilterPart fp{};
+    PipeSelectPart sp{};
+    PipeCompactPart cp{};
+    if (fs) {
+      fp = PipeFilterPart{fs->x, fs->x0, wsp<TopkCtrl>(fs->ws, o.ctrl),
+                          wsp<const uint32_t>(fs->ws, o.chist), wsp<uint32_t>(fs->ws, o.ghist),
+                          wsp<uint32_t>(fs->ws, o.segcnt), wsp<uint32_t>(fs->ws, o.cidx),
+                          wsp<uint32_t>(fs->ws, o.ckey), wsp<float>(fs->ws, o.cval),
+                          wsp<uint32_t>(fs->ws, o.blcnt), fs->r_out, fs->hint ? sig : 0u};
+      if (!fs->hint) {  // no prior window on this workspace: the sample launch, before the filter
+        KeySrc s{fs->x, fs->x0, nullptr, DPZ_ACC_NONE, 0};
+        DPZ_TIMED(DPZ_KT_TOPK_SAMPLE, st,
+                  sampled_sample_kernel<<<nsb, 256, 0, st>>>(
+                      s, n, wsp<TopkCtrl>(fs->ws, o.ctrl), wsp<uint32_t>(fs->ws, o.chist),
+                      wsp<uint32_t>(fs->ws, o.ghist), wsp<uint32_t>(fs->ws, o.blcnt), ReplaceJob{},
+                      nsb, 0));
+      }
+    }
+    if (ss)
+      sp = PipeSelectPart{ss->x, ss->x0, wsp<TopkCtrl>(ss->ws, o.ctrl),
+                          wsp<const uint32_t>(ss->ws, o.ghist),
+                          wsp<const uint32_t>(ss->ws, o.segcnt),
+                          wsp<const uint32_t>(ss->ws, o.cidx), wsp<const uint32_t>(ss->ws, o.ckey),
+                          wsp<uint32_t>(ss->ws, o.blkabove), wsp<uint32_t>(ss->ws, o.blcnt),
+                          wsp<uint32_t>(ss->ws, o.blkey), wsp<uint32_t>(ss->ws, o.blidx)};
+    if (cs) {
+      cp = PipeCompactPart{cs->x, cs->x0, wsp<TopkCtrl>(cs->ws, o.ctrl),
+                           wsp<uint32_t>(cs->ws, o.chist),
+                           wsp<const uint32_t>(cs->ws, o.blkabove),
+                           wsp<const uint32_t>(cs->ws, o.blcnt),
+                           wsp<const uint32_t>(cs->ws, o.blkey),
+                           wsp<const uint32_t>(cs->ws, o.blidx),
+                           wsp<const uint32_t>(cs->ws, o.segcnt),
+                           wsp<const uint32_t>(cs->ws, o.cidx), wsp<const uint32_t>(cs->ws, o.ckey),
+                           wsp<const float>(cs->ws, o.cval), wsp<uint32_t>(cs->ws, o.ghist),
+                           cs->idx_out, cs->val_out, cs->counter,
+                           ReplaceJob{cs->x, cs->r_idx, cs->r_val, r_k, n, cs->r_out, 0,
+                                      scatter_chunks(r_k), 0, 0, 1}};
+    }
+    const uint32_t nc = cs ? ncb + nsc : 0u, ns = ss ? nsel256 : 0u, nf = fs ? nb : 0u;
+    if (nc + ns + nf)
+      DPZ_TIMED(fs ? DPZ_KT_TOPK_FILTER : DPZ_KT_TOPK_COMPACT, st,
+                pipe_step_kernel<<<nc + ns + nf, 256, 0, st>>>(
+                    KeySrc{fp.x, fp.x0, nullptr, DPZ_ACC_NONE, 0}, fp.ctrl, fp.chist, fp.ghist,
+                    fp.segcnt, fp.cidx, fp.ckey, fp.cval, fp.blcnt, fp.out, fp.hsig,
+                    KeySrc{sp.x, sp.x0, nullptr, DPZ_ACC_NONE, 1}, sp.ctrl, sp.ghist, sp.segcnt,
+                    sp.cidx, sp.ckey, sp.blkabove, sp.blcnt, sp.blkey, sp.blidx,
+                    KeySrc{cp.x, cp.x0, nullptr, DPZ_ACC_NONE, 1}, cp.ctrl, cp.chist, cp.blkabove,
+                    cp.blcnt, cp.blkey, cp.blidx, cp.segcnt, cp.cidx, cp.ckey, cp.cval, cp.ghist,
+                    cp.idx_out, cp.val_out, cp.counter, cp.pj, n, k, r_lo, r_hi, g.W, g.B, g.R,
+                    g.CAP, nc, ns, ffirst ? nf : 0u, sig));
+    if (!full && fs) {  // compact-only pipelining: the select stays a launch of its own
+      KeySrc s{fs->x, fs->x0, nullptr, DPZ_ACC_NONE, 1};
+      DPZ_TIMED(DPZ_KT_TOPK_SELECT, st,
+                sampled_select_kernel<true><<<nsel1024, 1024, 0, st>>>(
+                    s, n, k, g.W, g.B, g.R, g.CAP, wsp<TopkCtrl>(fs->ws, o.ctrl),
+                    wsp<const uint32_t>(fs->ws, o.ghist), wsp<const uint32_t>(fs->ws, o.segcnt),
+                    wsp<const uint32_t>(fs->ws, o.cidx), wsp<const uint32_t>(fs->ws, o.ckey),
+                    wsp<uint32_t>(fs->ws, o.blkabove), wsp<uint32_t>(fs->ws, o.blcnt),
+                    wsp<uint32_t>(fs->ws, o.blkey), wsp<uint32_t>(fs->ws, o.blidx), ReplaceJob{}));
+    }
+  }
   return DPZ_OK;
 }
 

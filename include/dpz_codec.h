@@ -390,6 +390,27 @@ int dpz_encode_replace_batch(int m, int what, const float* const* x, const float
                              const float* const* r_val, int64_t r_k, float* const* r_out,
                              void* const* ws, size_t ws_bytes, void* const* dws, size_t dws_bytes,
                              int n_streams, const dpz_stream_t* streams);
+/* dpz_encode_replace_batch with the step batch pipelined where it can be.  ws_pipe: 2 * n_streams
+ * further top-k workspaces of ws_bytes each (zero-filled before their first use like ws;
+ * [2q], [2q + 1] belong to stream q).  Where every step of the call is a fused encode + replace
+ * (both operations, r_local[j] == x[j], another node's payload) on the sampled path, the steps
+ * of a stream rotate through ws[q], ws_pipe[2q], ws_pipe[2q + 1] (restarting at ws[q] on every
+ * call) and a step's selection tail runs inside the next steps' filter launches: one launch per
+ * step in steady state, identical results.  Any other call is enqueued as by
+ * dpz_encode_replace_batch.  ws_sig: a HOST array of 3 * n_streams words, zero before the first
+ * call and kept by the caller across calls ([3q] for ws[q], [3q + 1], [3q + 2] for stream q's
+ * ws_pipe): the library records which encode each workspace last held, and with DPZ_BATCH_HINT
+ * or DPZ_BATCH_HINT_ALL a step takes the prior window exactly where its workspace holds one of
+ * the step's own kind (any other step runs its sample launch).  *pipelined (HOST, may be NULL):
+ * the number of steps enqueued through the pipelined schedule (0 or m).                       */
+int dpz_encode_replace_batch_ws(int m, int what, const float* const* x, const float* const* x0,
+                                int64_t n, int64_t k, int32_t* const* counter,
+                                int32_t* const* idx_out, float* const* val_out,
+                                const float* const* r_local, const int32_t* const* r_idx,
+                                const float* const* r_val, int64_t r_k, float* const* r_out,
+                                void* const* ws, size_t ws_bytes, void* const* dws,
+                                size_t dws_bytes, int n_streams, const dpz_stream_t* streams,
+                                void* const* ws_pipe, uint32_t* ws_sig, int* pipelined);
 /* OR of the final status of every sampled-path encode run on this top-k workspace since the
  * last clear (0 = every one was final; nonzero = at least one missed and, if it was ASYNC and
  * not completed by dpz_topk_complete, published unverified output).  Synchronises `stream`;
