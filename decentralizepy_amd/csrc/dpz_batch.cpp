@@ -187,7 +187,7 @@ static int encode_replace_batch(int m, int what, const float* const* x,
     // A step is hinted only where its workspace has completed an encode of this signature
     // (ws_sig, kept by the caller across calls): an unprimed workspace gets its sample launch,
     // never a device-side miss
-    const uint32_t sig = dpz::hint_signature(n, k, true, DPZ_ACC_NONE, true);
+    const uint32_t sig = dpz::hint_signature(n, k, dpz::GEOM_PIPE, DPZ_ACC_NONE, true);
     std::vector<dpz::PipeStep> chain;
     for (int q = 0; q < n_streams && q < m; ++q) {
       if (!ws[q] || !ws_pipe[2 * q] || !ws_pipe[2 * q + 1]) return DPZ_ERR_ARG;

@@ -166,6 +166,22 @@ constexpr int W_MAX = DPZ_WMAX;    // wave segments (one wave streams one contig
 #endif
 constexpr int W_SMALL = DPZ_WSMALL;
 constexpr int64_t W_SMALL_N = (1 << 24) + (1 << 22);
+// The pipelined step batch (topk_pipe_chain) runs the sizes from W_PIPE_N up to W_SMALL_N at up
+// to W_PIPE segments: its merged kernel holds 5 blocks per CU since its parts overlay one LDS
+// arena, 1024 filter blocks are 4 per CU, and the tail's blocks ride in the launch itself, so they
+// need no CU slots of a neighbour launch.  Measured on MI355X, same box, alternated (DESIGN.md
+// §3.9): 64 MiB one-node step 49.2-49.4 us at 3072 -> 47.1-47.4 at 4096 (5120: 48.7-48.9, 8192:
+// 52.2-52.4), three codecs 41.5-42.0 -> 40.7-40.9 us.  Below W_PIPE_N the cap stays W_SMALL: at
+// C2 (11 M) 4096 measured SLOWER, one node 34.3-34.6 -> 35.3-35.7 us, three codecs 27.9-28.1 ->
+// 28.1-28.4 (segments of 2,686 elements against 3,581).  Two sizes were measured; the rule
+// changes the grid only at and above the larger one.
+#ifndef DPZ_WPIPE
+#define DPZ_WPIPE 4096
+#endif
+constexpr int W_PIPE = DPZ_WPIPE;
+constexpr int64_t W_PIPE_N = 1 << 24;
+// which grid a call runs at (fast_geom, ws_layout, hint_signature)
+enum : int { GEOM_LONE = 0, GEOM_SHARED = 1, GEOM_PIPE = 2 };
 constexpr int FG = DPZ_FG;         // float4 groups of 256 elements a filter wave loads at once
 #ifndef DPZ_FOCC
 #define DPZ_FOCC 8
@@ -204,13 +220,22 @@ struct FastGeom {
 // W_SMALL_N elements the filter grid is capped at W_SMALL segments so the other streams' kernels
 // find free CU slots; a lone codec (one stream) takes the full W_MAX grid, the faster one alone
 // (C2 filter 18.8 vs 20.6 us).
-static inline FastGeom fast_geom(int64_t n, int64_t k = 0, bool shared = false) {
+// geom = GEOM_PIPE: the pipelined step batch's grid, capped at W_PIPE segments from W_PIPE_N
+// elements up, where the shared grid is capped at W_SMALL.
+static inline FastGeom fast_geom(int64_t n, int64_t k = 0, int geom = GEOM_LONE) {
   FastGeom g;
   int64_t W = (n + W_MIN_RANGE - 1) / W_MIN_RANGE;
   // DPZ_WLONE=N caps a lone codec's grid at N segments (diagnostic build, A/B)
   const int64_t wlone = DPZ_KNOB_INT(WLONE, 0);
-  const int64_t wmax = (shared && n <= W_SMALL_N)
-                           ? W_SMALL
+  // DPZ_WPIPE=N: the pipelined grid's cap (diagnostic build, A/B; 3072 against 4096 is 3 against
+  // 4 filter blocks per CU)
+  // (when set it holds at every size up to W_SMALL_N)
+  const int64_t wpipe_knob = DPZ_KNOB_INT(WPIPE, 0);
+  const int64_t wpipe = (wpipe_knob > 0 && wpipe_knob <= W_MAX)
+                            ? wpipe_knob
+                            : (n >= W_PIPE_N ? (int64_t)W_PIPE : (int64_t)W_SMALL);
+  const int64_t wmax = (geom != GEOM_LONE && n <= W_SMALL_N)
+                           ? (geom == GEOM_PIPE ? wpipe : (int64_t)W_SMALL)
                            : ((wlone > 0 && wlone < W_MAX) ? wlone : W_MAX);
   if (W > wmax) W = wmax;
   if (W < 1) W = 1;
@@ -241,12 +266,12 @@ struct WsLayout {
   FastGeom fg;
 };
 
-static inline WsLayout ws_layout(int64_t n, int64_t k = 0, bool shared = false) {
+static inline WsLayout ws_layout(int64_t n, int64_t k = 0, int geom = GEOM_LONE) {
   WsLayout L;
   size_t o = 0;
   L.ex_nblk = (n + EX_CHUNK - 1) / EX_CHUNK;
   if (L.ex_nblk < 1) L.ex_nblk = 1;
-  L.fg = fast_geom(n > 0 ? n : 1, k, shared);
+  L.fg = fast_geom(n > 0 ? n : 1, k, geom);
   L.ctrl = o; o += align256(sizeof(TopkCtrl));
   L.chist = o; o += align256(CB * 4);  // must be zero before the first sampled call (self-cleaning)
   L.ex_hist = o; o += align256(4096 * 4);
@@ -270,8 +295,12 @@ static inline WsLayout ws_layout(int64_t n, int64_t k = 0, bool shared = false) 
 
 // Workspace bytes a caller must provide: enough for either grid (the flags choose per call).
 static inline size_t ws_bytes_needed(int64_t n, int64_t k) {
-  const size_t a = ws_layout(n, k, false).total, b = ws_layout(n, k, true).total;
-  return a > b ? a : b;
+  size_t m = 0;
+  for (int geom = GEOM_LONE; geom <= GEOM_PIPE; ++geom) {
+    const size_t t = ws_layout(n, k, geom).total;
+    if (t > m) m = t;
+  }
+  return m;
 }
 
 struct EncodeArgs {
@@ -297,9 +326,9 @@ struct EncodeArgs {
 };
 // Signature of a sampled call's geometry and key source: a prior-round window is only taken from
 // a call with the same one (the same workspace layout, so its window histogram copies are zero)
-static inline uint32_t hint_signature(int64_t n, int64_t k, bool shared, int acc_mode, bool x0) {
+static inline uint32_t hint_signature(int64_t n, int64_t k, int geom, int acc_mode, bool x0) {
   uint64_t h = 1469598103934665603ull;
-  const uint64_t v[5] = {(uint64_t)n, (uint64_t)k, shared ? 1ull : 0ull, (uint64_t)acc_mode,
+  const uint64_t v[5] = {(uint64_t)n, (uint64_t)k, (uint64_t)geom, (uint64_t)acc_mode,
                          x0 ? 1ull : 0ull};
   for (int i = 0; i < 5; ++i) h = (h ^ v[i]) * 1099511628211ull;
   return (uint32_t)(h ^ (h >> 32)) | 1u;

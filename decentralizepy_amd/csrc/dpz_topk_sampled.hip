@@ -432,14 +432,24 @@ __device__ __forceinline__ void hint_window(uint32_t T, uint32_t* lo, uint32_t* 
 // block 0 then does the sample launch's per-call resets (status, boundary sub-list counters; the
 // window-histogram copies were left zero by the previous call's compact); an invalid prior makes
 // the call miss at once (every block leaves, select and compact see the status).
+// The LDS of one block of a part (filter / select / compact): the body takes a reference to it, a
+// stand-alone kernel declares exactly its own, and the merged step kernel (pipe_step_kernel)
+// declares one union of the three, since a block only ever runs one part.  A body writes every
+// LDS word before it reads it (DPZ_PIPE_POISON, diagnostic build: the arena starts as all-ones).
+struct FilterLds {
+  uint32_t h[HBR];
+  uint32_t win[4];
+  uint32_t wsum[16];
+  uint32_t st[4][3 * STAGE];
+};
+
 template <int SRC, int CP, int D, int OCC, bool XNT>
-__device__ __forceinline__ void sampled_filter_pipe_kernel_body(KeySrc s, int64_t n, uint32_t r_lo, uint32_t r_hi, int64_t W, int64_t R, int64_t CAP, TopkCtrl* ctrl, const uint32_t* __restrict__ chist, uint32_t* ghist, uint32_t* segcnt, uint32_t* cidx, uint32_t* ckey, float* cval, float* __restrict__ copy_out, FoldBase fb, uint32_t hsig, uint32_t* blcnt, int val_h, const uint32_t BID) {
+__device__ __forceinline__ void sampled_filter_pipe_kernel_body(FilterLds& M, KeySrc s, int64_t n, uint32_t r_lo, uint32_t r_hi, int64_t W, int64_t R, int64_t CAP, TopkCtrl* ctrl, const uint32_t* __restrict__ chist, uint32_t* ghist, uint32_t* segcnt, uint32_t* cidx, uint32_t* ckey, float* cval, float* __restrict__ copy_out, FoldBase fb, uint32_t hsig, uint32_t* blcnt, int val_h, const uint32_t BID) {
   static_assert(D >= 2, "at least one group in flight");
   typedef float v4f __attribute__((ext_vector_type(4)));
-  __shared__ uint32_t h[HBR];
-  __shared__ uint32_t win[4];
-  __shared__ uint32_t wsum[16];
-  __shared__ uint32_t st[4][3 * STAGE];
+  uint32_t* const h = M.h;
+  uint32_t* const win = M.win;
+  uint32_t* const wsum = M.wsum;
   const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
   STAMP_T0(5);
   for (int b = threadIdx.x; b < HBR; b += 256) h[b] = 0;
@@ -531,7 +541,7 @@ __device__ __forceinline__ void sampled_filter_pipe_kernel_body(KeySrc s, int64_
     ctrl->hi = hi;
     ctrl->shift = shift;
   }
-  WaveList L{cidx + seg * CAP, ckey + seg * CAP, cval ? cval + seg * CAP : nullptr, st[wid], 0u,
+  WaveList L{cidx + seg * CAP, ckey + seg * CAP, cval ? cval + seg * CAP : nullptr, M.st[wid], 0u,
              0u};
   uint32_t run = 0;
   bool dense = false;
@@ -594,7 +604,8 @@ __device__ __forceinline__ void sampled_filter_pipe_kernel_body(KeySrc s, int64_
 
 template <int SRC, int CP, int D, int OCC, bool XNT>
 __global__ void __launch_bounds__(256, OCC) sampled_filter_pipe_kernel(KeySrc s, int64_t n, uint32_t r_lo, uint32_t r_hi, int64_t W, int64_t R, int64_t CAP, TopkCtrl* ctrl, const uint32_t* __restrict__ chist, uint32_t* ghist, uint32_t* segcnt, uint32_t* cidx, uint32_t* ckey, float* cval, float* __restrict__ copy_out, FoldBase fb, uint32_t hsig, uint32_t* blcnt, int val_h) {
-  sampled_filter_pipe_kernel_body<SRC, CP, D, OCC, XNT>(s, n, r_lo, r_hi, W, R, CAP, ctrl, chist, ghist, segcnt, cidx, ckey, cval, copy_out, fb, hsig, blcnt, val_h, (uint32_t)blockIdx.x);
+  __shared__ FilterLds lds;
+  sampled_filter_pipe_kernel_body<SRC, CP, D, OCC, XNT>(lds, s, n, r_lo, r_hi, W, R, CAP, ctrl, chist, ghist, segcnt, cidx, ckey, cval, copy_out, fb, hsig, blcnt, val_h, (uint32_t)blockIdx.x);
 }
 
 // Wave-level threshold bin from the global window histogram gh (LDS, HB fine bins + the
@@ -643,8 +654,16 @@ __device__ __forceinline__ bool wave_bstar(const uint32_t* gh, uint32_t above, u
 // segments per block, four fine bins per thread for the histogram sum; four blocks stand for one
 // 1024-thread block (the same blkabove zero padding), still one atomic per block onto sub-list
 // block % 16 (W = 8192: 1024 blocks, 64 arrivals per counter).
+template <int NT>
+struct SelectLds {
+  uint32_t gh[GH_STRIDE];  // read as uint4 (wave_bstar): offset 0 of a 16-byte aligned object
+  uint32_t lkey[SEL_LCAP], lidx[SEL_LCAP];
+  uint32_t fbabove[NT / 64 * 2 / 4];
+  uint32_t lcnt, gbase, sb_bstar, sb_need, sb_ok;
+};
+
 template <bool VEC, int NT = 1024>
-__device__ __forceinline__ void sampled_select_kernel_body(KeySrc s, int64_t n, int64_t k, int64_t W, int64_t B, int64_t R, int64_t CAP, TopkCtrl* ctrl, const uint32_t* __restrict__ ghist, const uint32_t* __restrict__ segcnt, const uint32_t* __restrict__ cidx, const uint32_t* __restrict__ ckey, uint32_t* blkabove, uint32_t* blcnt, uint32_t* blkey, uint32_t* blidx, ReplaceJob pj, const uint32_t BID) {
+__device__ __forceinline__ void sampled_select_kernel_body(SelectLds<NT>& M, KeySrc s, int64_t n, int64_t k, int64_t W, int64_t B, int64_t R, int64_t CAP, TopkCtrl* ctrl, const uint32_t* __restrict__ ghist, const uint32_t* __restrict__ segcnt, const uint32_t* __restrict__ cidx, const uint32_t* __restrict__ ckey, uint32_t* blkabove, uint32_t* blcnt, uint32_t* blkey, uint32_t* blidx, ReplaceJob pj, const uint32_t BID) {
   static_assert(NT == 1024 || NT == 256, "select block: 1024 or 256 threads");
   constexpr int SS = NT / 64 * 2;  // wave segments per block
   constexpr int NQ = HB / NT;      // fine bins per thread
@@ -657,10 +676,15 @@ __device__ __forceinline__ void sampled_select_kernel_body(KeySrc s, int64_t n, 
   }
   STAMP_MIN(6);
   STAMP_T0(8);
-  __shared__ __attribute__((aligned(16))) uint32_t gh[GH_STRIDE];
-  __shared__ uint32_t fbabove[SS / 4];
-  __shared__ uint32_t lkey[SEL_LCAP], lidx[SEL_LCAP];
-  __shared__ uint32_t lcnt, gbase, sb_bstar, sb_need, sb_ok;
+  uint32_t* const gh = M.gh;
+  uint32_t* const fbabove = M.fbabove;
+  uint32_t* const lkey = M.lkey;
+  uint32_t* const lidx = M.lidx;
+  uint32_t& lcnt = M.lcnt;
+  uint32_t& gbase = M.gbase;
+  uint32_t& sb_bstar = M.sb_bstar;
+  uint32_t& sb_need = M.sb_need;
+  uint32_t& sb_ok = M.sb_ok;
   const int t = threadIdx.x, wid = t >> 6, lane = t & 63;
   const int64_t seg0 = (int64_t)BID * SS + wid * 2;
   const uint32_t cnt0 = seg0 < W ? segcnt[seg0] : 0u;
@@ -682,13 +706,16 @@ __device__ __forceinline__ void sampled_select_kernel_body(KeySrc s, int64_t n, 
   // histogram copies (bins t and, for t == 0, the above-window bin HB), then chunks 1 .. PFS-1
   // of segments with more than 64 candidates — all loads issued before any sum is formed
   static_assert(HB == 1024, "select: NQ fine bins per thread + the above-window bin");
-  uint32_t v[GH_COPIES][NQ], va[GH_COPIES];
+  // (the above-window bin of copy t in thread t < GH_COPIES, summed across wave 0's lanes below:
+  // one register instead of GH_COPIES in thread 0)
+  static_assert((GH_COPIES & (GH_COPIES - 1)) == 0 && GH_COPIES <= 64, "one copy per lane");
+  uint32_t v[GH_COPIES][NQ];
 #pragma unroll
   for (int c = 0; c < GH_COPIES; ++c) {
 #pragma unroll
     for (int q = 0; q < NQ; ++q) v[c][q] = ghist[c * GH_STRIDE + q * NT + t];
-    va[c] = t == 0 ? ghist[c * GH_STRIDE + HB] : 0u;
   }
+  const uint32_t va = t < GH_COPIES ? ghist[t * GH_STRIDE + HB] : 0u;
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const int64_t sg = seg0 + u;
@@ -706,9 +733,9 @@ __device__ __forceinline__ void sampled_select_kernel_body(KeySrc s, int64_t n, 
   }
   if (fstatus) return;  // uniform over the grid
   {
-    uint32_t suma = 0;
+    uint32_t suma = va;
 #pragma unroll
-    for (int c = 0; c < GH_COPIES; ++c) suma += va[c];
+    for (int d = 1; d < GH_COPIES; d <<= 1) suma += __shfl_xor(suma, d, 64);
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
       uint32_t sum = 0;
@@ -835,7 +862,8 @@ __device__ __forceinline__ void sampled_select_kernel_body(KeySrc s, int64_t n, 
 
 template <bool VEC>
 __global__ void __launch_bounds__(1024) sampled_select_kernel(KeySrc s, int64_t n, int64_t k, int64_t W, int64_t B, int64_t R, int64_t CAP, TopkCtrl* ctrl, const uint32_t* __restrict__ ghist, const uint32_t* __restrict__ segcnt, const uint32_t* __restrict__ cidx, const uint32_t* __restrict__ ckey, uint32_t* blkabove, uint32_t* blcnt, uint32_t* blkey, uint32_t* blidx, ReplaceJob pj) {
-  sampled_select_kernel_body<VEC>(s, n, k, W, B, R, CAP, ctrl, ghist, segcnt, cidx, ckey, blkabove, blcnt, blkey, blidx, pj, (uint32_t)blockIdx.x);
+  __shared__ __attribute__((aligned(16))) SelectLds<1024> lds;
+  sampled_select_kernel_body<VEC>(lds, s, n, k, W, B, R, CAP, ctrl, ghist, segcnt, cidx, ckey, blkabove, blcnt, blkey, blidx, pj, (uint32_t)blockIdx.x);
 }
 
 // Boundary entry j (0 <= j < nb) of the 16 sub-lists: sub-list sb with subbase[sb] <= j.
@@ -1126,19 +1154,30 @@ static_assert(32 % SL_PF == 0, "the planes are read in whole steps");
 // selected bits into an LDS row (R <= SL_RMAX, R a multiple of 32: the segment owns whole
 // words), then writes every word of the row to selmask and adds it to the bit-sliced counter
 // (planes[p * nwords + w], carry-propagated plane by plane) with coalesced accesses.
+template <int SPW, bool SL>
+struct CompactLds {
+  uint32_t slrows[SL ? 4 : 1][SL ? (int)(SL_RMAX / 32) : 1];
+  uint32_t wcnt[CompactCfg<SPW>::CSEG];
+  uint32_t subbase[NSUB + 1];
+  uint32_t flag, spec;
+  uint64_t wsum64[4];
+  alignas(16) ResolveLds RL;
+  alignas(16) uint32_t bsk[BLDS];
+  alignas(16) uint32_t bsi[BLDS];
+};
+
 template <bool VEC, bool PLAIN, int SPW, bool SL>
-__device__ __forceinline__ void sampled_compact_kernel_body(KeySrc s, int64_t n, int64_t k, int64_t W, int64_t R, int64_t CAP, TopkCtrl* ctrl, uint32_t* chist, const uint32_t* __restrict__ blkabove, const uint32_t* __restrict__ blcnt, const uint32_t* __restrict__ blkey, const uint32_t* __restrict__ blidx, const uint32_t* __restrict__ segcnt, const uint32_t* __restrict__ cidx, const uint32_t* __restrict__ ckey, const float* __restrict__ cval, const float* vals_src, int32_t* idx_out, float* val_out, int32_t* counter, float* rewind, int32_t* status_out, ReplaceJob pj, int64_t nrep_first, int val_h, uint32_t* selmask, uint32_t* planes, int64_t nwords, uint32_t* ghist, uint32_t sig, const uint32_t BID) {
+__device__ __forceinline__ void sampled_compact_kernel_body(CompactLds<SPW, SL>& M, KeySrc s, int64_t n, int64_t k, int64_t W, int64_t R, int64_t CAP, TopkCtrl* ctrl, uint32_t* chist, const uint32_t* __restrict__ blkabove, const uint32_t* __restrict__ blcnt, const uint32_t* __restrict__ blkey, const uint32_t* __restrict__ blidx, const uint32_t* __restrict__ segcnt, const uint32_t* __restrict__ cidx, const uint32_t* __restrict__ ckey, const float* __restrict__ cval, const float* vals_src, int32_t* idx_out, float* val_out, int32_t* counter, float* rewind, int32_t* status_out, ReplaceJob pj, int64_t nrep_first, int val_h, uint32_t* selmask, uint32_t* planes, int64_t nwords, uint32_t* ghist, uint32_t sig, const uint32_t BID) {
   constexpr int CSEG = CompactCfg<SPW>::CSEG;
   constexpr int PFC = CompactCfg<SPW>::PFC;
-  constexpr int SLW = SL ? (int)(SL_RMAX / 32) : 1;
-  __shared__ uint32_t slrows[SL ? 4 : 1][SLW];
-  __shared__ uint32_t wcnt[CSEG];
-  __shared__ uint32_t subbase[NSUB + 1];
-  __shared__ uint32_t flag, spec;
-  __shared__ uint64_t wsum64[4];
-  __shared__ ResolveLds RL;
-  __shared__ __attribute__((aligned(16))) uint32_t bsk[BLDS];
-  __shared__ __attribute__((aligned(16))) uint32_t bsi[BLDS];
+  uint32_t* const wcnt = M.wcnt;
+  uint32_t* const subbase = M.subbase;
+  uint32_t& flag = M.flag;
+  uint32_t& spec = M.spec;
+  uint64_t* const wsum64 = M.wsum64;
+  ResolveLds& RL = M.RL;
+  uint32_t* const bsk = M.bsk;
+  uint32_t* const bsi = M.bsi;
   const int64_t CB_ = (W + CSEG - 1) / CSEG;
   const int64_t B = (W + 3) / 4;  // filter blocks (above counts)
   // co-scheduled replace decode: its blocks after compact's own, or (nrep_first > 0) before
@@ -1157,7 +1196,8 @@ __device__ __forceinline__ void sampled_compact_kernel_body(KeySrc s, int64_t n,
   const int64_t seg0 = (int64_t)blk * CSEG + wid * SPW;
   // every independent load first: control words, sub-list counts, above counts, own candidates
   const uint32_t status = ctrl->status;
-  const uint32_t need = ctrl->need, lo = ctrl->lo, shift = ctrl->shift, bstar = ctrl->bstar;
+  const uint32_t need_l = ctrl->need, lo_l = ctrl->lo, shift_l = ctrl->shift,
+                 bstar_l = ctrl->bstar;
   const uint32_t sc = t < NSUB ? blcnt[t] : 0u;
   // the first SPEC entries of every boundary sub-list, loaded with the counts (thread t: sub-list
   // t / SPEC, slot t % SPEC) instead of after them: when no sub-list holds more (the usual case,
@@ -1237,7 +1277,7 @@ __device__ __forceinline__ void sampled_compact_kernel_body(KeySrc s, int64_t n,
     if (t < NSUB) subbase[t] = ex;
     if (t == 0) {
       subbase[NSUB] = tot;
-      flag = (over || tot > (uint32_t)BCAP || need == 0 || need > tot) ? 1u : 0u;
+      flag = (over || tot > (uint32_t)BCAP || need_l == 0 || need_l > tot) ? 1u : 0u;
       spec = spec_ok ? 1u : 0u;
     }
   }
@@ -1250,6 +1290,14 @@ __device__ __forceinline__ void sampled_compact_kernel_body(KeySrc s, int64_t n,
     }
     return;
   }
+  // the control words and the segment counts are wave-uniform and have arrived by the barrier:
+  // from here on they live in scalar registers
+  const uint32_t need = __builtin_amdgcn_readfirstlane(need_l);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane(lo_l);
+  const uint32_t shift = __builtin_amdgcn_readfirstlane(shift_l);
+  const uint32_t bstar = __builtin_amdgcn_readfirstlane(bstar_l);
+#pragma unroll
+  for (int u = 0; u < SPW; ++u) cnt[u] = __builtin_amdgcn_readfirstlane(cnt[u]);
   STAMP_T0(1);
   Bound bd{blkey, blidx, subbase, bsk, bsi, subbase[NSUB]};
   if (spec) {  // every boundary entry is in a speculative register (nb <= 256 <= BLDS)
@@ -1263,6 +1311,8 @@ __device__ __forceinline__ void sampled_compact_kernel_body(KeySrc s, int64_t n,
   }
   uint32_t T, icut;
   block_resolve(bd, need, lo + (bstar << shift), shift, RL, &T, &icut);
+  T = __builtin_amdgcn_readfirstlane(T);  // block-uniform (read from LDS): scalar registers
+  icut = __builtin_amdgcn_readfirstlane(icut);
   STAMP_T0(2);
   // selected boundary entries before this block / overall, plus the above counts
   const uint32_t bstart = (uint32_t)((int64_t)blk * CSEG * R);
@@ -1274,7 +1324,8 @@ __device__ __forceinline__ void sampled_compact_kernel_body(KeySrc s, int64_t n,
   });
   const uint64_t tot2 = block_sum64(((uint64_t)(abv_all + sb_all) << 32) |
                                         (uint64_t)(abv_before + sb_before), wsum64);
-  const uint32_t boff = (uint32_t)tot2, grand = (uint32_t)(tot2 >> 32);
+  const uint32_t boff = __builtin_amdgcn_readfirstlane((uint32_t)tot2);
+  const uint32_t grand = __builtin_amdgcn_readfirstlane((uint32_t)(tot2 >> 32));
   if (blk == 0 && t == 0) {
     ctrl->T = T;
     ctrl->icut = icut;
@@ -1355,7 +1406,8 @@ __device__ __forceinline__ void sampled_compact_kernel_body(KeySrc s, int64_t n,
   STAMP_T0(3);
   uint32_t run = boff;
   for (int w = 0; w < wid * SPW; ++w) run += wcnt[w];
-  uint32_t* const slrow = SL ? slrows[wid] : nullptr;
+  run = __builtin_amdgcn_readfirstlane(run);  // wave-uniform
+  uint32_t* const slrow = SL ? M.slrows[wid] : nullptr;
 #pragma unroll
   for (int u = 0; u < SPW; ++u) {
     const int64_t seg = seg0 + u;
@@ -1449,7 +1501,8 @@ __device__ __forceinline__ void sampled_compact_kernel_body(KeySrc s, int64_t n,
 
 template <bool VEC, bool PLAIN, int SPW, bool SL>
 __global__ void __launch_bounds__(256, SPW >= 8 ? 1 : 4) sampled_compact_kernel(KeySrc s, int64_t n, int64_t k, int64_t W, int64_t R, int64_t CAP, TopkCtrl* ctrl, uint32_t* chist, const uint32_t* __restrict__ blkabove, const uint32_t* __restrict__ blcnt, const uint32_t* __restrict__ blkey, const uint32_t* __restrict__ blidx, const uint32_t* __restrict__ segcnt, const uint32_t* __restrict__ cidx, const uint32_t* __restrict__ ckey, const float* __restrict__ cval, const float* vals_src, int32_t* idx_out, float* val_out, int32_t* counter, float* rewind, int32_t* status_out, ReplaceJob pj, int64_t nrep_first, int val_h, uint32_t* selmask, uint32_t* planes, int64_t nwords, uint32_t* ghist, uint32_t sig) {
-  sampled_compact_kernel_body<VEC, PLAIN, SPW, SL>(s, n, k, W, R, CAP, ctrl, chist, blkabove, blcnt, blkey, blidx, segcnt, cidx, ckey, cval, vals_src, idx_out, val_out, counter, rewind, status_out, pj, nrep_first, val_h, selmask, planes, nwords, ghist, sig, (uint32_t)blockIdx.x);
+  __shared__ __attribute__((aligned(16))) CompactLds<SPW, SL> lds;
+  sampled_compact_kernel_body<VEC, PLAIN, SPW, SL>(lds, s, n, k, W, R, CAP, ctrl, chist, blkabove, blcnt, blkey, blidx, segcnt, cidx, ckey, cval, vals_src, idx_out, val_out, counter, rewind, status_out, pj, nrep_first, val_h, selmask, planes, nwords, ghist, sig, (uint32_t)blockIdx.x);
 }
 
 // Fractions of a co-scheduled replace job's chunks carried by sample / select / compact;
@@ -1700,8 +1753,10 @@ __global__ void __launch_bounds__(256, OCC) nodes_filter_kernel(
   const uint32_t node = blockIdx.x / nb, bid = blockIdx.x % nb;
   const EncNode e = tab[node];
   KeySrc s{e.x, e.x0, nullptr, DPZ_ACC_NONE, 0};
+  __shared__ FilterLds lds;
   sampled_filter_pipe_kernel_body<1, 0, D, OCC, true>(
-      s, n, r_lo, r_hi, W, R, CAP, wsp<TopkCtrl>(e.ws, o.ctrl), wsp<const uint32_t>(e.ws, o.chist),
+      lds, s, n, r_lo, r_hi, W, R, CAP, wsp<TopkCtrl>(e.ws, o.ctrl),
+      wsp<const uint32_t>(e.ws, o.chist),
       wsp<uint32_t>(e.ws, o.ghist), wsp<uint32_t>(e.ws, o.segcnt), wsp<uint32_t>(e.ws, o.cidx),
       wsp<uint32_t>(e.ws, o.ckey), wsp<float>(e.ws, o.cval), nullptr, FoldBase{}, hsig,
       wsp<uint32_t>(e.ws, o.blcnt), 0, bid);
@@ -1714,8 +1769,10 @@ __global__ void __launch_bounds__(1024) nodes_select_kernel(const EncNode* __res
   const uint32_t node = blockIdx.x / nsel, bid = blockIdx.x % nsel;
   const EncNode e = tab[node];
   KeySrc s{e.x, e.x0, nullptr, DPZ_ACC_NONE, 1};
+  __shared__ __attribute__((aligned(16))) SelectLds<1024> lds;
   sampled_select_kernel_body<true>(
-      s, n, k, W, B, R, CAP, wsp<TopkCtrl>(e.ws, o.ctrl), wsp<const uint32_t>(e.ws, o.ghist),
+      lds, s, n, k, W, B, R, CAP, wsp<TopkCtrl>(e.ws, o.ctrl),
+      wsp<const uint32_t>(e.ws, o.ghist),
       wsp<const uint32_t>(e.ws, o.segcnt), wsp<const uint32_t>(e.ws, o.cidx),
       wsp<const uint32_t>(e.ws, o.ckey), wsp<uint32_t>(e.ws, o.blkabove),
       wsp<uint32_t>(e.ws, o.blcnt), wsp<uint32_t>(e.ws, o.blkey), wsp<uint32_t>(e.ws, o.blidx),
@@ -1740,8 +1797,9 @@ __global__ void __launch_bounds__(256, 4) nodes_compact_kernel(const EncNode* __
   int32_t* const counter = SL || DPZ_NODES_NO_COUNTER ? nullptr : e.counter;
   uint32_t* const selmask = SL ? reinterpret_cast<uint32_t*>(e.pad) : nullptr;
   uint32_t* const planes = SL ? reinterpret_cast<uint32_t*>(e.counter) : nullptr;
+  __shared__ __attribute__((aligned(16))) CompactLds<2, SL> lds;
   sampled_compact_kernel_body<true, PLAIN, 2, SL>(
-      s, n, k, W, R, CAP, wsp<TopkCtrl>(e.ws, o.ctrl), wsp<uint32_t>(e.ws, o.chist),
+      lds, s, n, k, W, R, CAP, wsp<TopkCtrl>(e.ws, o.ctrl), wsp<uint32_t>(e.ws, o.chist),
       wsp<const uint32_t>(e.ws, o.blkabove), wsp<const uint32_t>(e.ws, o.blcnt),
       wsp<const uint32_t>(e.ws, o.blkey), wsp<const uint32_t>(e.ws, o.blidx),
       wsp<const uint32_t>(e.ws, o.segcnt), wsp<const uint32_t>(e.ws, o.cidx),
@@ -1855,9 +1913,41 @@ struct PipeCompactPart {
   ReplaceJob pj;   // the step's received payload, scattered into its out
 };
 
+// One LDS arena per block: a block runs one part, so the parts' LDS overlays (as three sets of
+// function-local arrays they added up to 38.8 KB, 4 blocks per CU, and the filter's 3 blocks per
+// CU left the whole tail one slot).  The merged launch's arena is the filter's 16.5 KB; a drain
+// launch (no filter part) has the select's 12.3 KB.
+template <bool FILTER>
+union PipeLds {
+  FilterLds f;
+  SelectLds<256> s;
+  CompactLds<2, false> c;
+};
+template <>
+union PipeLds<false> {
+  SelectLds<256> s;
+  CompactLds<2, false> c;
+};
+
+// Blocks per CU (= waves per SIMD) the merged kernel's registers are sized for: its 81 VGPRs
+// (allocated as 88) allow 5.  DPZ_PIPE_OCC=6 (diagnostic build, A/B) is the 80-register form
+// (79 VGPRs, no scratch, no spill): it measured no faster on the one-node step (46.7-47.2 against
+// 47.1-47.4 us) and 0.7-1.0 us slower with three codecs, so 5 ships
+constexpr int PIPE_OCC = 5;
+#ifdef DPZ_DIAG
+constexpr bool PIPE_DIAG = true;
+#else
+constexpr bool PIPE_DIAG = false;
+#endif
+
 // grid: the nf filter blocks, then nc compact + scatter blocks, then nsel select blocks; with
-// nf == 0 the filter's blocks (if any) come after the tail's
-__global__ void __launch_bounds__(256, 4) pipe_step_kernel(
+// nf == 0 the filter's blocks (if any) come after the tail's.  FILTER = false: a drain launch,
+// the tail's parts only (a symbol of its own in a kernel trace).
+// poison (DPZ_PIPE_POISON, diagnostic build only): every thread fills the whole arena with
+// 0xFFFFFFFF before the block's part starts, so a part that read LDS it had not written, i.e.
+// what another part's block left there, would compute from all-ones (tests/test_gpu_pipe_arena.py)
+template <bool FILTER, int OCC>
+__global__ void __launch_bounds__(256, OCC) pipe_step_kernel(
     KeySrc fs, TopkCtrl* f_ctrl, const uint32_t* __restrict__ f_chist, uint32_t* f_ghist,
     uint32_t* f_segcnt, uint32_t* f_cidx, uint32_t* f_ckey, float* f_cval, uint32_t* f_blcnt,
     float* __restrict__ f_out, uint32_t f_hsig,
@@ -1872,57 +1962,70 @@ __global__ void __launch_bounds__(256, 4) pipe_step_kernel(
     const float* __restrict__ c_cval, uint32_t* c_ghist, int32_t* c_idx_out, float* c_val_out,
     int32_t* c_counter, ReplaceJob c_pj,
     int64_t n, int64_t k, uint32_t r_lo, uint32_t r_hi, int64_t W, int64_t B, int64_t R,
-    int64_t CAP, uint32_t nc, uint32_t nsel, uint32_t nf, uint32_t sig) {
+    int64_t CAP, uint32_t nc, uint32_t nsel, uint32_t nf, uint32_t sig, uint32_t poison) {
+  __shared__ __attribute__((aligned(16))) PipeLds<FILTER> lds;
+  static_assert(sizeof(lds) % 4 == 0, "the arena is poisoned in 32-bit words");
+  if (PIPE_DIAG && poison) {
+    uint32_t* const w = reinterpret_cast<uint32_t*>(&lds);
+    for (uint32_t j = 0; j < (uint32_t)(sizeof(lds) / 4); ++j) w[j] = 0xFFFFFFFFu;
+    __syncthreads();
+  }
   uint32_t bid = blockIdx.x;
   // nf != 0: the nf filter blocks hold the lowest indices, then the tail's (filter first)
-  if (nf) {
-    if (bid < nf) {
-      sampled_filter_pipe_kernel_body<1, 1, 4, 4, true>(
-          fs, n, r_lo, r_hi, W, R, CAP, f_ctrl, f_chist, f_ghist, f_segcnt, f_cidx, f_ckey, f_cval,
-          f_out, FoldBase{}, f_hsig, f_blcnt, 0, bid);
-      return;
+  if constexpr (FILTER) {
+    if (nf) {
+      if (bid < nf) {
+        sampled_filter_pipe_kernel_body<1, 1, 4, 4, true>(
+            lds.f, fs, n, r_lo, r_hi, W, R, CAP, f_ctrl, f_chist, f_ghist, f_segcnt, f_cidx,
+            f_ckey, f_cval, f_out, FoldBase{}, f_hsig, f_blcnt, 0, bid);
+        return;
+      }
+      bid -= nf;
     }
-    bid -= nf;
   }
   if (bid < nc) {
     sampled_compact_kernel_body<true, false, 2, false>(
-        cs, n, k, W, R, CAP, c_ctrl, c_chist, c_blkabove, c_blcnt, c_blkey, c_blidx, c_segcnt,
-        c_cidx, c_ckey, c_cval, cs.x, c_idx_out, c_val_out, c_counter, nullptr, nullptr, c_pj, 0,
-        0, nullptr, nullptr, 0, c_ghist, sig, bid);
+        lds.c, cs, n, k, W, R, CAP, c_ctrl, c_chist, c_blkabove, c_blcnt, c_blkey, c_blidx,
+        c_segcnt, c_cidx, c_ckey, c_cval, cs.x, c_idx_out, c_val_out, c_counter, nullptr, nullptr,
+        c_pj, 0, 0, nullptr, nullptr, 0, c_ghist, sig, bid);
     return;
   }
   bid -= nc;
   if (bid < nsel) {
-    sampled_select_kernel_body<true, 256>(ss, n, k, W, B, R, CAP, s_ctrl, s_ghist, s_segcnt,
-                                          s_cidx, s_ckey, s_blkabove, s_blcnt, s_blkey, s_blidx,
-                                          ReplaceJob{}, bid);
+    sampled_select_kernel_body<true, 256>(lds.s, ss, n, k, W, B, R, CAP, s_ctrl, s_ghist,
+                                          s_segcnt, s_cidx, s_ckey, s_blkabove, s_blcnt, s_blkey,
+                                          s_blidx, ReplaceJob{}, bid);
     return;
   }
   bid -= nsel;
-  if (nf) return;
-  sampled_filter_pipe_kernel_body<1, 1, 4, 4, true>(fs, n, r_lo, r_hi, W, R, CAP, f_ctrl, f_chist,
-                                                    f_ghist, f_segcnt, f_cidx, f_ckey, f_cval,
-                                                    f_out, FoldBase{}, f_hsig, f_blcnt, 0, bid);
+  if constexpr (FILTER) {
+    if (nf) return;
+    sampled_filter_pipe_kernel_body<1, 1, 4, 4, true>(
+        lds.f, fs, n, r_lo, r_hi, W, R, CAP, f_ctrl, f_chist, f_ghist, f_segcnt, f_cidx, f_ckey,
+        f_cval, f_out, FoldBase{}, f_hsig, f_blcnt, 0, bid);
+  }
 }
 
 bool topk_pipe_ok(int64_t n, int64_t k, size_t ws_bytes) {
-  // the sampled path with the scattered-atomic counter form (sparse alpha) at the shared-grid
-  // geometry: at most 4096 segments, so the filter part runs at depth 4 with 4 waves per SIMD
-  // and leaves wave slots to the tail's blocks
+  // the sampled path with the scattered-atomic counter form (sparse alpha) at the pipelined
+  // grid: at most W_PIPE segments (1024 filter blocks, 4 per CU), so the filter part runs at
+  // depth 4 and the merged kernel's fifth block per CU is left to the tail's blocks
+  // (DPZ_WPIPE, diagnostic build, may raise the cap for A/B)
   if (n <= 0 || n >= (int64_t(1) << 31) || !use_sampled(n, k) || k > n / 32) return false;
   if (ws_bytes < ws_bytes_needed(n, k)) return false;
-  return fast_geom(n, k, true).W <= 4096 && DPZ_KNOB_INT(FILTER_PIPE, 1) > 0;
+  const int64_t wcap = DPZ_KNOB_INT(WPIPE, 0) > W_PIPE ? (int64_t)W_MAX : (int64_t)W_PIPE;
+  return fast_geom(n, k, GEOM_PIPE).W <= wcap && DPZ_KNOB_INT(FILTER_PIPE, 1) > 0;
 }
 
 int topk_pipe_chain(int p, const PipeStep* c, int64_t n, int64_t k, int64_t r_k, int mode,
                     hipStream_t st) {
   if (p < 1 || !c || !topk_pipe_ok(n, k, ws_bytes_needed(n, k)) || r_k < 1 || r_k > n)
     return DPZ_ERR_ARG;
-  const WsLayout L = ws_layout(n, k, true);
+  const WsLayout L = ws_layout(n, k, GEOM_PIPE);
   const FastGeom& g = L.fg;
   const WsOff o{L.ctrl, L.chist, L.f_ghist, L.f_segcnt, L.f_blkabove, L.f_cidx, L.f_ckey,
                 L.f_cval, L.f_blcnt, L.f_blkey, L.f_blidx};
-  const uint32_t sig = hint_signature(n, k, true, DPZ_ACC_NONE, true);
+  const uint32_t sig = hint_signature(n, k, GEOM_PIPE, DPZ_ACC_NONE, true);
   const int nsb = SMP_NCHUNK / 16;  // 256-thread sample blocks
   const uint32_t nb = (uint32_t)g.B;
   const uint32_t nsel1024 = (uint32_t)((g.W + SEL_SEGS - 1) / SEL_SEGS);
@@ -1932,11 +2035,21 @@ int topk_pipe_chain(int p, const PipeStep* c, int64_t n, int64_t k, int64_t r_k,
   uint32_t r_lo, r_hi;
   window_ranks(n, k, &r_lo, &r_hi);
   const bool full = mode >= 2;
-  // The filter's blocks hold the lowest indices: at 4 blocks per CU (38.8 KB of LDS each) the
-  // tail's ~1400 blocks of a 64 MiB step, dispatched first, took every slot and the filter waited
-  // for them (one-node step 54.8 us; filter first 50.3 us, 60.4 us unpipelined, MI355X, DESIGN.md
-  // §3.9).  DPZ_PIPE_ORDER=0 (diagnostic build, A/B): the tail's blocks first
+  // The filter's blocks hold the lowest indices: the tail's ~1600 blocks of a 64 MiB step,
+  // dispatched first, take every slot (5 per CU) and the filter waits for them (one-node step
+  // 51.3-51.6 us; filter first 47.1-47.4 us, MI355X, same box).
+  // DPZ_PIPE_ORDER=0 (diagnostic build, A/B): the tail's blocks first
   const bool ffirst = DPZ_KNOB_INT(PIPE_ORDER, 1) != 0;
+  // a launch with a filter part, and a drain launch (the tail's parts only)
+  auto* kmerged = pipe_step_kernel<true, PIPE_OCC>;
+  auto* kdrain = pipe_step_kernel<false, PIPE_OCC>;
+#ifdef DPZ_DIAG
+  if (DPZ_KNOB_INT(PIPE_OCC, PIPE_OCC) == 6) {
+    kmerged = pipe_step_kernel<true, 6>;
+    kdrain = pipe_step_kernel<false, 6>;
+  }
+#endif
+  const uint32_t poison = DPZ_KNOB_INT(PIPE_POISON, 0) != 0 ? 1u : 0u;
   // the last launch carries the compact of c_{p-1}: launch p + 1 (full), launch p (compact only)
   const int last = full ? p + 1 : p;
   for (int i = 0; i <= last; ++i) {
@@ -1986,7 +2099,7 @@ int topk_pipe_chain(int p, const PipeStep* c, int64_t n, int64_t k, int64_t r_k,
     const uint32_t nc = cs ? ncb + nsc : 0u, ns = ss ? nsel256 : 0u, nf = fs ? nb : 0u;
     if (nc + ns + nf)
       DPZ_TIMED(fs ? DPZ_KT_TOPK_FILTER : DPZ_KT_TOPK_COMPACT, st,
-                pipe_step_kernel<<<nc + ns + nf, 256, 0, st>>>(
+                (fs ? kmerged : kdrain)<<<nc + ns + nf, 256, 0, st>>>(
                     KeySrc{fp.x, fp.x0, nullptr, DPZ_ACC_NONE, 0}, fp.ctrl, fp.chist, fp.ghist,
                     fp.segcnt, fp.cidx, fp.ckey, fp.cval, fp.blcnt, fp.out, fp.hsig,
                     KeySrc{sp.x, sp.x0, nullptr, DPZ_ACC_NONE, 1}, sp.ctrl, sp.ghist, sp.segcnt,
@@ -1994,7 +2107,7 @@ int topk_pipe_chain(int p, const PipeStep* c, int64_t n, int64_t k, int64_t r_k,
                     KeySrc{cp.x, cp.x0, nullptr, DPZ_ACC_NONE, 1}, cp.ctrl, cp.chist, cp.blkabove,
                     cp.blcnt, cp.blkey, cp.blidx, cp.segcnt, cp.cidx, cp.ckey, cp.cval, cp.ghist,
                     cp.idx_out, cp.val_out, cp.counter, cp.pj, n, k, r_lo, r_hi, g.W, g.B, g.R,
-                    g.CAP, nc, ns, ffirst ? nf : 0u, sig));
+                    g.CAP, nc, ns, ffirst ? nf : 0u, sig, poison));
     if (!full && fs) {  // compact-only pipelining: the select stays a launch of its own
       KeySrc s{fs->x, fs->x0, nullptr, DPZ_ACC_NONE, 1};
       DPZ_TIMED(DPZ_KT_TOPK_SELECT, st,

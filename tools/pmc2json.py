@@ -37,6 +37,11 @@ def short(name):
     if base == "sampled_filter_pipe_kernel" and "<" in head:
         cp = head.split("<")[1].split(",")[1].strip()
         return FILTER_CP.get(cp, "topk_filter")
+    # pipe_step_kernel<FILTER, OCC>: FILTER = false is a drain launch (the tail's parts only),
+    # listed where KernelTimer times it
+    if base == "pipe_step_kernel" and head.split("<")[1:2] and \
+            head.split("<")[1].split(",")[0].strip() in ("false", "0"):
+        return "topk_compact"
     return NAMES.get(base)
 
 
