@@ -351,6 +351,16 @@ class RingCounter(DeviceCounter):
             self.segs = [0]
         return self._t
 
+    @staticmethod
+    def flush_many(rings):
+        """:meth:`flush` of several rings (distinct counters) on the current stream in one
+        native call (dpz_counter_flush_batch)."""
+        from . import codec
+        pend = [r for r in rings if len(r.segs) > 1]
+        codec.counter_flush_batch([(r._t, r.ring, r.segs, r._ws) for r in pend])
+        for r in pend:
+            r.segs = [0]
+
     @property
     def device_tensor(self):
         return self.flush()

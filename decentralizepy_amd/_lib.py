@@ -46,6 +46,7 @@ DPZ_EW_MHCOMBINE = 4
 DPZ_COUNTER_AUTO = 0
 DPZ_COUNTER_SCATTER = 1
 DPZ_COUNTER_SWEEP = 2
+DPZ_COUNTER_SPARSE = 3
 DPZ_OK = 0
 DPZ_ERR_ARG = 1001
 DPZ_ERR_WORKSPACE = 1002
@@ -56,6 +57,14 @@ _c_void_p = ctypes.c_void_p
 _i64 = ctypes.c_int64
 _int = ctypes.c_int
 _size = ctypes.c_size_t
+
+
+class CounterItem(ctypes.Structure):
+    """dpz_counter_item: one counter of a dpz_counter_flush_batch table."""
+    _fields_ = [("counter", _c_void_p), ("n", _i64), ("ring", _c_void_p),
+                ("seg_off", ctypes.POINTER(_i64)), ("m", _int), ("ws", _c_void_p),
+                ("ws_bytes", _size)]
+
 
 # name -> (restype, argtypes); must match include/dpz_codec.h
 SIGNATURES = {
@@ -86,6 +95,7 @@ SIGNATURES = {
     "dpz_counter_flush_workspace_bytes": (_size, [_i64]),
     "dpz_counter_flush": (_int, [_c_void_p, _i64, _c_void_p, ctypes.POINTER(_i64), _int, _int,
                                  _c_void_p, _size, _c_void_p]),
+    "dpz_counter_flush_batch": (_int, [ctypes.POINTER(CounterItem), _int, _int, _c_void_p]),
     "dpz_dwt_sym2_rewind": (_int, [_c_void_p, _c_void_p, _i64, _int, _c_void_p, _c_void_p,
                                    _c_void_p]),
     "dpz_dwt_haar_rewind": (_int, [_c_void_p, _c_void_p, _i64, _int, _c_void_p, _c_void_p,

@@ -23,7 +23,7 @@ __all__ = ["DPZ_ACC_NONE", "DPZ_ACC_ACCUMULATE", "DPZ_ACC_ADD", "DPZ_EW_SUB", "D
            "KernelTimer", "NodeStepBatch", "topk_sticky_status", "rfft", "irfft", "fft_native", "cplx_key",
            "cplx_gather", "cplx_pair_indices", "lz4_compress", "lz4_decompress", "lz4_frame_info",
            "delta_i32", "running_sum_i32", "mask_words", "topk_encode_sliced", "counter_unslice",
-           "counter_slice", "rewind_apply", "counter_flush"]
+           "counter_slice", "rewind_apply", "counter_flush", "counter_flush_batch"]
 
 
 def _ptr(t):
@@ -302,6 +302,35 @@ def counter_flush(counter, ring, seg_off, mode=_lib.DPZ_COUNTER_AUTO, workspace=
     return counter
 
 
+def counter_flush_batch(items, mode=_lib.DPZ_COUNTER_AUTO):
+    """:func:`counter_flush` of several counters on the current stream in one native call
+    (dpz_counter_flush_batch): ``items`` holds ``(counter, ring, seg_off, workspace)`` per
+    counter, the counters distinct and each with a workspace of its own (``None``: allocated
+    here).  The counters that take a tiled form share one bounds and one tile launch."""
+    tab, keep = [], []
+    for counter, ring, seg_off, workspace in items:
+        _require(counter, torch.int32, "counter")
+        _require(ring, torch.int32, "ring")
+        m = len(seg_off) - 1
+        if m < 1:
+            continue
+        if int(seg_off[-1]) > ring.numel():
+            raise ValueError("counter_flush_batch: segments past the ring")
+        need = int(_lib.lib().dpz_counter_flush_workspace_bytes(counter.numel()))
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty(need, dtype=torch.uint8, device=counter.device)
+        offs = (ctypes.c_int64 * (m + 1))(*[int(v) for v in seg_off])
+        keep.append((offs, workspace))
+        tab.append(_lib.CounterItem(counter.data_ptr(), counter.numel(), ring.data_ptr(), offs, m,
+                                    workspace.data_ptr(), workspace.numel()))
+    if not tab:
+        return
+    arr = (_lib.CounterItem * len(tab))(*tab)
+    check(_lib.lib().dpz_counter_flush_batch(arr, len(tab), int(mode),
+                                             _stream(items[0][0].device)),
+          "dpz_counter_flush_batch")
+
+
 def rewind_apply(acc, sel_mask):
     """acc[i] = 0 where sel_mask has bit i (the deferred rewind on its own, dpz_rewind_apply)."""
     _require(acc, torch.float32, "acc")
@@ -436,13 +465,16 @@ class NodeStepBatch:
         return r.slot(self.k)
 
     def flush_rings(self):
-        """Every node's deferred counter updates into its counter, on its stream."""
+        """Every node's deferred counter updates into its counter, on its stream: the nodes of a
+        stream in one batched flush."""
         if self._rings is None:
             return
-        for j, r in enumerate(self._rings):
-            if r.pending_rounds():
-                with torch.cuda.stream(self._tstreams[j % self._S]):
-                    r.flush()
+        from ._device import RingCounter
+        for s in range(self._S):  # one native call per stream (dpz_counter_flush_batch)
+            mine = [r for r in self._rings[s::self._S] if r.pending_rounds()]
+            if mine:
+                with torch.cuda.stream(self._tstreams[s]):
+                    RingCounter.flush_many(mine)
 
     def run(self, what=_lib.DPZ_BATCH_ENCODE | _lib.DPZ_BATCH_DECODE, m=None):
         """``what`` with DPZ_BATCH_HINT: the encodes take the prior window (DPZ_TOPK_HINT) —

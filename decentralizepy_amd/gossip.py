@@ -299,19 +299,21 @@ class GossipRound:
         return codec.counter_unslice(self._planes[j], self.N, out=out)
 
     def _flush_ring(self):
-        """The ring's committed rounds into every owned node's int32 counter (dpz_counter_flush,
-        one call per node: its rounds are adjacent in the ring), the ring emptied."""
+        """The ring's committed rounds into every owned node's int32 counter
+        (dpz_counter_flush_batch: one call, a node's rounds are adjacent in the ring), the ring
+        emptied."""
         u = self._ring_used
         if u == 0:
             return
         from . import _lib, codec
-        if self._flush_ws is None:
+        own = self.hi - self.lo
+        if self._flush_ws is None:  # one scratch row per owned node: they share the launches
             need = max(256, int(_lib.lib().dpz_counter_flush_workspace_bytes(self.N)))
-            self._flush_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            need = -(-need // 256) * 256
+            self._flush_ws = torch.empty((own, need), dtype=torch.uint8, device=self.device)
         offs = [i * self.k for i in range(u + 1)]
-        for j in range(self.hi - self.lo):
-            codec.counter_flush(self._counter[j], self._ring[j].view(-1), offs,
-                                workspace=self._flush_ws)
+        codec.counter_flush_batch([(self._counter[j], self._ring[j].view(-1), offs,
+                                    self._flush_ws[j]) for j in range(own)])
         self._ring_used = 0
 
     def _ring_next(self):

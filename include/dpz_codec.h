@@ -268,15 +268,37 @@ int dpz_rewind_apply(float* acc, const uint32_t* sel_mask, int64_t n, dpz_stream
  * seg_off: HOST int64[m + 1], seg_off[0] = 0, ascending; each segment strictly ascending indices
  * in [0, n) (an index outside is skipped).  mode DPZ_COUNTER_SCATTER: one atomic per entry;
  * DPZ_COUNTER_SWEEP: every tile of the counter read, incremented in LDS and written once (8n
- * coalesced bytes + 8 per entry, per 64 segments; ws: device scratch of
- * dpz_counter_flush_workspace_bytes(n) bytes, only the sweep uses it); DPZ_COUNTER_AUTO picks
- * the cheaper.                                                                                 */
+ * coalesced bytes + 8 per entry, per 64 segments); DPZ_COUNTER_SPARSE: the sweep's tiles, but
+ * only the 64-byte sectors of the counter that an entry touches are read, added to and written
+ * (a sector without an entry is neither read nor written; no global atomic).  ws: device scratch
+ * of dpz_counter_flush_workspace_bytes(n) bytes, used by the sweep and the sparse form.
+ * DPZ_COUNTER_AUTO takes the scatter form for few entries per counter and the sparse form
+ * otherwise (the more counters a call flushes, the sooner: they share the launches); the dense
+ * sweep measured no faster than the sparse form and is taken only on request.  The sparse form
+ * counts a launch's additions to a counter in a byte: segments must be strictly ascending.
+ * dpz_counter_flush_batch: the same for `count` counters (HOST table; distinct counters, each
+ * with its own ws) on one stream: the tiles of all counters that take the same tiled form run
+ * in one bounds launch and one tile launch per 8 counters and 64 segments; a counter that
+ * takes the scatter form keeps its own launch.  Every item is validated before the first
+ * launch.                                                                                       */
 #define DPZ_COUNTER_AUTO 0
 #define DPZ_COUNTER_SCATTER 1
 #define DPZ_COUNTER_SWEEP 2
+#define DPZ_COUNTER_SPARSE 3
+typedef struct dpz_counter_item {
+  int32_t* counter;
+  int64_t n;
+  const int32_t* ring;
+  const int64_t* seg_off; /* HOST int64[m + 1] */
+  int m;
+  void* ws;
+  size_t ws_bytes;
+} dpz_counter_item;
 size_t dpz_counter_flush_workspace_bytes(int64_t n);
 int dpz_counter_flush(int32_t* counter, int64_t n, const int32_t* ring, const int64_t* seg_off,
                       int m, int mode, void* ws, size_t ws_bytes, dpz_stream_t stream);
+int dpz_counter_flush_batch(const dpz_counter_item* items, int count, int mode,
+                            dpz_stream_t stream);
 
 /* Batched decode + Metro-Hastings fold over n_payloads neighbour payloads.
  * Replaces reference sharing/PartialModel.py:257-303 (T = cat(local); T[idx] = params),

@@ -19,7 +19,7 @@ NAMES = {"sampled_sample_kernel": "topk_sample", "sampled_filter_kernel": "topk_
          "fold_kernel": "fold", "fold_group_kernel": "fold_group", "fold_slots_kernel": "fold_slots",
          "fold_walk_kernel": "fold_walk", "fold_walk_groups_kernel": "fold_walk", "replace_kernel": "fold", "dwt_kernel": "dwt", "dwt4_kernel": "dwt",
          "haar_dwt_kernel": "haar_dwt", "haar_idwt_kernel": "haar_idwt",
-         "idwt_kernel": "idwt", "counter_sweep_kernel": "counter_flush",
+         "idwt_kernel": "idwt", "counter_sweep_kernel": "counter_flush", "counter_sparse_kernel": "counter_flush",
          "counter_bounds_kernel": "counter_bounds", "counter_scatter_kernel": "counter_flush",
          "fold_merge_kernel": "fold_merge", "ft_pass_kernel": "fft_pass", "ft_pass_ip_kernel": "fft_pass_ip",
          "ft_r2c_post_kernel": "fft_r2c_post", "ft_c2r_pre_kernel": "fft_c2r_pre"}
