@@ -205,6 +205,19 @@ SIGNATURES = {
     "dpz_running_sum_workspace_bytes": (_size, [_i64]),
     "dpz_running_sum_i32": (_int, [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _size,
                                    _c_void_p]),
+    "dpz_mt_chunk_elems": (_i64, []),
+    "dpz_mt_coarse_chunks": (_i64, []),
+    "dpz_mt_raw_host": (_int, [ctypes.c_uint32, _i64, _i64, _c_void_p]),
+    "dpz_mt_rank_entries": (_i64, [_i64]),
+    "dpz_mt_mask_workspace_bytes": (_size, [_i64]),
+    "dpz_mt_mask": (_int, [ctypes.c_uint32, ctypes.c_float, _i64, _c_void_p, _c_void_p,
+                           _c_void_p, _c_void_p, _size, _c_void_p]),
+    "dpz_mask_gather": (_int, [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                               _c_void_p]),
+    "dpz_mask_decode_average": (_int, [_c_void_p, _i64, _int, ctypes.POINTER(_c_void_p),
+                                       ctypes.POINTER(_c_void_p), ctypes.POINTER(_c_void_p),
+                                       ctypes.POINTER(ctypes.c_float), ctypes.c_float, _int,
+                                       _c_void_p, _c_void_p]),
 }
 
 _lib = None

@@ -23,7 +23,8 @@ __all__ = ["DPZ_ACC_NONE", "DPZ_ACC_ACCUMULATE", "DPZ_ACC_ADD", "DPZ_EW_SUB", "D
            "KernelTimer", "NodeStepBatch", "topk_sticky_status", "rfft", "irfft", "fft_native", "cplx_key",
            "cplx_gather", "cplx_pair_indices", "lz4_compress", "lz4_decompress", "lz4_frame_info",
            "delta_i32", "running_sum_i32", "mask_words", "topk_encode_sliced", "counter_unslice",
-           "counter_slice", "rewind_apply", "counter_flush", "counter_flush_batch"]
+           "counter_slice", "rewind_apply", "counter_flush", "counter_flush_batch", "mt_mask",
+           "mt_rank_entries", "mask_gather", "mask_decode_average"]
 
 
 def _ptr(t):
@@ -1141,6 +1142,134 @@ def running_sum_i32(d, dtype=torch.int64, workspace=None):
                                         ws.numel(), _stream(d.device))
     check(rc, "dpz_running_sum_i32")
     return out[:k]
+
+
+def mt_rank_entries(n):
+    """int32 entries of the rank table that goes with a mask over n elements (opaque)."""
+    return int(_lib.lib().dpz_mt_rank_entries(int(n)))
+
+
+def _mt_ws(workspace, device, need):
+    workspace = workspace or Workspace(device)
+    buf = getattr(workspace, "mbuf", None)
+    if buf is None or buf.numel() < max(need, 256):
+        buf = workspace.mbuf = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+    return buf
+
+
+def mt_mask(seed, alpha, n, device, mask=None, rank_tab=None, count=None, workspace=None):
+    """SubSampling's Bernoulli mask (reference sharing/SubSampling.py:148-157, 265-294):
+    ``torch.rand(n, generator=g) <= alpha`` after ``g.manual_seed(seed)``, bit for bit, from a
+    jump-ahead MT19937 on the device (the generator is seeded with ``seed & 0xffffffff`` and
+    ``alpha`` compared as the fp32 torch rounds it to).  Returns ``(mask int32[mask_words(n)],
+    rank_tab int32[mt_rank_entries(n)], count int64[1])``, all on the device; nothing blocks."""
+    n = int(n)
+    device = torch.device(device)
+    if mask is None:
+        mask = torch.empty(mask_words(n), dtype=torch.int32, device=device)
+    if rank_tab is None:
+        rank_tab = torch.empty(mt_rank_entries(n), dtype=torch.int32, device=device)
+    if count is None:
+        count = torch.empty(1, dtype=torch.int64, device=device)
+    _require(mask, torch.int32, "mask")
+    _require(rank_tab, torch.int32, "rank_tab")
+    _require(count, torch.int64, "count")
+    if mask.numel() < mask_words(n) or rank_tab.numel() < mt_rank_entries(n):
+        raise ValueError("mask / rank_tab too small for n")
+    ws = _mt_ws(workspace, device, int(_lib.lib().dpz_mt_mask_workspace_bytes(n)))
+    with torch.cuda.device(device):  # the jump tables are kept per device
+        rc = _lib.lib().dpz_mt_mask(int(seed) & 0xffffffff, float(np.float32(alpha)), n,
+                                    _ptr(mask), _ptr(rank_tab), _ptr(count), _ptr(ws),
+                                    ws.numel(), _stream(device))
+    check(rc, "dpz_mt_mask")
+    return mask, rank_tab, count
+
+
+def mask_gather(x, mask, rank_tab, vals, counter=None, count=None):
+    """``vals[:count] = x[mask]`` in index order and, with ``counter`` (int32[n]),
+    ``counter[mask] += 1`` (reference SubSampling.py:158-159).  ``vals`` is caller-owned and
+    holds at least the mask's count of values: a caller that has read the count passes it as
+    ``count`` (a Python int) and a shorter ``vals`` is refused here, before the launch."""
+    _require(x, torch.float32, "x")
+    _require(mask, torch.int32, "mask")
+    _require(rank_tab, torch.int32, "rank_tab")
+    _require(vals, torch.float32, "vals")
+    _require(counter, torch.int32, "counter")
+    n = x.numel()
+    if mask.numel() < mask_words(n) or rank_tab.numel() < mt_rank_entries(n):
+        raise ValueError("mask / rank_tab too small for x")
+    if counter is not None and counter.numel() != n:
+        raise ValueError("counter and x differ in length")
+    if count is not None and vals.numel() < int(count):
+        raise ValueError(f"vals holds {vals.numel()} values for a mask of {int(count)} elements")
+    # an empty selection writes nothing, but the ABI wants a pointer
+    rc = _lib.lib().dpz_mask_gather(_ptr(x), n, _ptr(mask), _ptr(rank_tab),
+                                    _ptr(vals if vals.numel() else x), _ptr(counter),
+                                    _stream(x.device))
+    check(rc, "dpz_mask_gather")
+    return vals
+
+
+MASK_FOLD_MAX = 16  # payloads per dpz_mask_decode_average launch
+
+
+def mask_decode_average(local, payloads, weights, w_self=None, out=None, counts=None):
+    """Metro-Hastings fold over SubSampling payloads (reference Sharing.py:156-229 over
+    SubSampling.deserialized_model), bit-exact in the reference's fp32 order.
+
+    payloads : list of ``(mask, rank_tab, vals)`` device tensors; ``vals`` must hold exactly the
+               mask's count of values
+    weights  : per-payload weights (Python floats, rounded to fp32 like torch does)
+    w_self   : weight of the local term, or None for the server form (no self term)
+    counts   : the masks' counts as Python ints, when the caller has read them: a payload whose
+               ``vals`` differs in length raises ValueError before anything is launched (without
+               it the caller answers for the lengths: the kernel indexes vals by mask rank)
+
+    More than 16 payloads are folded 16 at a time, each launch continuing the running total of
+    the one before it (DPZ_FOLD_ACCUMULATE) and the last adding the self term: the same
+    roundings in the same order as one pass.
+    """
+    _require(local, torch.float32, "local")
+    n = local.numel()
+    if out is None:
+        out = torch.empty_like(local)
+    _require(out, torch.float32, "out")
+    if out.numel() != n or out.data_ptr() == local.data_ptr():
+        raise ValueError("out must hold n values and not be local")
+    npay = len(payloads)
+    if npay < 1:
+        raise ValueError("no payloads")
+    if counts is not None:
+        for i, ((_, _, vals), c) in enumerate(zip(payloads, counts)):
+            if vals.numel() != int(c):
+                raise ValueError(f"payload {i}: {vals.numel()} params for a mask of {int(c)} "
+                                 "elements")
+    for i, (mask, rank_tab, vals) in enumerate(payloads):
+        _require(mask, torch.int32, "mask")
+        _require(rank_tab, torch.int32, "rank_tab")
+        _require(vals, torch.float32, "vals")
+        if mask.numel() < mask_words(n) or rank_tab.numel() < mt_rank_entries(n):
+            raise ValueError("mask / rank_tab too small for local")
+    for lo in range(0, npay, MASK_FOLD_MAX):
+        part = payloads[lo:lo + MASK_FOLD_MAX]
+        last = lo + MASK_FOLD_MAX >= npay
+        m_arr = (ctypes.c_void_p * len(part))()
+        r_arr = (ctypes.c_void_p * len(part))()
+        v_arr = (ctypes.c_void_p * len(part))()
+        w_arr = (ctypes.c_float * len(part))()
+        for i, (mask, rank_tab, vals) in enumerate(part):
+            if vals.numel() == 0:  # an empty selection: never read, but the ABI wants a pointer
+                vals = local
+            m_arr[i], r_arr[i], v_arr[i] = mask.data_ptr(), rank_tab.data_ptr(), vals.data_ptr()
+            w_arr[i] = float(weights[lo + i])
+        flags = ((DPZ_FOLD_SELF if last and w_self is not None else 0)
+                 | (_lib.DPZ_FOLD_ACCUMULATE if lo else 0))
+        rc = _lib.lib().dpz_mask_decode_average(
+            _ptr(local), n, len(part), m_arr, r_arr, v_arr, w_arr,
+            float(w_self) if w_self is not None else 0.0, flags, _ptr(out),
+            _stream(local.device))
+        check(rc, "dpz_mask_decode_average")
+    return out
 
 
 class KernelTimer:

@@ -669,6 +669,57 @@ size_t dpz_running_sum_workspace_bytes(int64_t k);
 int dpz_running_sum_i32(const int32_t* in, int64_t k, int64_t* out64, int32_t* out32, void* ws,
                         size_t ws_bytes, dpz_stream_t stream);
 
+/* ---- SubSampling: the sender's Bernoulli mask rebuilt from its seed (sharing/SubSampling.py) ---
+ * The reference's mask is `torch.rand(n, generator=g) <= alpha` after g.manual_seed(s): MT19937
+ * (init_genrand(s & 0xffffffff)), one tempered 32-bit output per element, u = (out & 0xFFFFFF) *
+ * 2^-24 as fp32, so bit j = (out_j & 0xFFFFFF) <= floor((double)(float)alpha * 2^24).  The
+ * kernels reproduce that bit string in parallel by jump-ahead: chunk c of dpz_mt_chunk_elems()
+ * elements starts from the state t^(c * chunk) mod phi gives (phi: MT19937's characteristic
+ * polynomial; tables of jump polynomials are built on the host on first use and copied once to
+ * each device that uses them, the one allocation the library makes besides the FFT twiddles).
+ * So a dpz_mt_mask call that needs table rows its device does not have yet BLOCKS: it builds
+ * the missing rows on the host (about 0.2 s for all that 2^24 elements need, once per process),
+ * allocates on the first call per device and copies the rows with a synchronous hipMemcpy.
+ * Such a call must not sit inside a stream capture: run one mask of the largest n first.
+ * Above dpz_mt_coarse_chunks() chunks a coarse launch first jumps to every
+ * coarse_chunks * chunk_elems boundary.  n < 2^31 elements.
+ * dpz_mt_raw_host (host only, no device call): the tempered outputs [start, start + count) of
+ * seed's stream into out (HOST), through the same jump tables — a jump to each enclosing chunk,
+ * then stepping — so the GF(2) code can be checked without a GPU.
+ * dpz_mt_mask: mask (dpz_mask_words(n) words, bit b of word w <-> element 32w + b, trailing bits
+ * zero), rank_tab (dpz_mt_rank_entries(n) int32, opaque: exclusive popcounts that turn a mask
+ * bit into its position among the selected elements) and *count_dev (DEVICE int64, the number
+ * selected).  alpha is the fp32 the sender's Python float rounds to; alpha < 0 or NaN selects
+ * nothing, alpha >= 1 everything.  ws: dpz_mt_mask_workspace_bytes(n).
+ * dpz_mask_gather: vals[rank(j)] = x[j] for every selected j in index order (`concated[mask]`,
+ * SubSampling.py:158) and, with counter != NULL, counter[j] += 1 (:159).
+ * dpz_mask_decode_average: the Metro-Hastings fold (sharing/Sharing.py:156-190) over payloads
+ * deserialised by SubSampling.deserialized_model (T = local; T[mask_i] = vals_i), in the
+ * reference's fp32 order: t = w_0 v_0, t = t + w_i v_i, out = t + w_self local with
+ * v_i = bit_i ? vals_i[rank_i(j)] : local[j].  mask / rank_tab / vals / w: HOST arrays of
+ * n_payloads entries (1 .. 16, more is DPZ_ERR_UNSUPPORTED; device pointers inside).  flags:
+ * DPZ_FOLD_SELF (without it the server form, Sharing.py:200-229: no self term) and
+ * DPZ_FOLD_ACCUMULATE (out holds the running total t of earlier payloads on entry and the fold
+ * continues from it: more than 16 payloads are folded 16 at a time, the self term in the last
+ * call, with the same roundings as one pass); any other bit is DPZ_ERR_ARG.  vals_i must hold
+ * the mask's count of values: the caller checks that before the call.  out may not overlap
+ * local.
+ * The three device entry points return DPZ_ERR_ARG before any device call for n < 1, null
+ * pointers or n_payloads < 1.                                                                  */
+int64_t dpz_mt_chunk_elems(void);
+int64_t dpz_mt_coarse_chunks(void);
+int dpz_mt_raw_host(uint32_t seed, int64_t start, int64_t count, uint32_t* out);
+int64_t dpz_mt_rank_entries(int64_t n);
+size_t dpz_mt_mask_workspace_bytes(int64_t n);
+int dpz_mt_mask(uint32_t seed, float alpha, int64_t n, uint32_t* mask, int32_t* rank_tab,
+                int64_t* count_dev, void* ws, size_t ws_bytes, dpz_stream_t stream);
+int dpz_mask_gather(const float* x, int64_t n, const uint32_t* mask, const int32_t* rank_tab,
+                    float* vals, int32_t* counter, dpz_stream_t stream);
+int dpz_mask_decode_average(const float* local, int64_t n, int n_payloads,
+                            const uint32_t* const* mask, const int32_t* const* rank_tab,
+                            const float* const* vals, const float* w, float w_self, int flags,
+                            float* out, dpz_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
