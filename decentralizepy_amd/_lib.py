@@ -218,6 +218,12 @@ SIGNATURES = {
                                        ctypes.POINTER(_c_void_p), ctypes.POINTER(_c_void_p),
                                        ctypes.POINTER(ctypes.c_float), ctypes.c_float, _int,
                                        _c_void_p, _c_void_p]),
+    "dpz_quant_workspace_bytes": (_size, [_i64]),
+    "dpz_quant_block_elems": (_i64, []),
+    "dpz_quant_encode": (_int, [_c_void_p, _i64, _i64, _c_void_p, _i64, _c_void_p, _c_void_p,
+                                _size, _c_void_p]),
+    "dpz_quant_decode": (_int, [_c_void_p, _i64, _i64, _int, ctypes.c_double, _c_void_p,
+                                _c_void_p]),
 }
 
 _lib = None

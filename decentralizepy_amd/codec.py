@@ -24,7 +24,8 @@ __all__ = ["DPZ_ACC_NONE", "DPZ_ACC_ACCUMULATE", "DPZ_ACC_ADD", "DPZ_EW_SUB", "D
            "cplx_gather", "cplx_pair_indices", "lz4_compress", "lz4_decompress", "lz4_frame_info",
            "delta_i32", "running_sum_i32", "mask_words", "topk_encode_sliced", "counter_unslice",
            "counter_slice", "rewind_apply", "counter_flush", "counter_flush_batch", "mt_mask",
-           "mt_rank_entries", "mask_gather", "mask_decode_average"]
+           "mt_rank_entries", "mask_gather", "mask_decode_average", "quant_encode", "quant_decode",
+           "quant_block_elems", "QuantInfo"]
 
 
 def _ptr(t):
@@ -1270,6 +1271,97 @@ def mask_decode_average(local, payloads, weights, w_self=None, out=None, counts=
             _stream(local.device))
         check(rc, "dpz_mask_decode_average")
     return out
+
+
+class QuantInfo:
+    """The info record of a ``quant_encode``: what the pack kernel derived on the device."""
+
+    __slots__ = ("status", "w", "padding", "scale", "norm", "max_abs", "abs_sum", "offset")
+
+    def __init__(self, words):
+        f = np.asarray(words, dtype=np.int32).view(np.float32)
+        self.status, self.w, self.padding = int(words[0]), int(words[1]), int(words[2])
+        self.scale, self.norm, self.max_abs, self.abs_sum = f[3], f[4], f[5], f[6]
+        self.offset = int(np.asarray(words, dtype=np.int32).view(np.uint32)[7])
+
+
+def quant_block_elems():
+    """Values one block of the quantiser's pack kernel covers (the tests' edge sizes)."""
+    return int(_lib.lib().dpz_quant_block_elems())
+
+
+def _quant_ws(workspace, device, need):
+    workspace = workspace or Workspace(device)
+    buf = getattr(workspace, "qbuf", None)
+    if buf is None or buf.numel() < max(need, 256):
+        buf = workspace.qbuf = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+    return buf
+
+
+def quant_encode(x, k, workspace=None):
+    """The reference quantiser (compression/Quantization.py:28-91) of a device fp32 vector with
+    ``float_precision`` k: ``(body, info)``, the packed stream body as a device uint8 tensor
+    (4-byte aligned, exactly ceil(n * w / 8) bytes) and a :class:`QuantInfo`.  The statistics and
+    the pack kernels run back to back; the one synchronisation is the read of the info record,
+    which the caller's copy of the body needs anyway.  The body is allocated for the widest
+    field k can give.  ValueError for an empty, all-zero or non-finite input and for k outside
+    [1, 2^30]; TypeError for a k that is no int."""
+    _require(x, torch.float32, "x")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise TypeError(f"float_precision must be an int, got {type(k).__name__}")
+    k = int(k)
+    if not 1 <= k <= 2 ** 30:
+        raise ValueError("float_precision must be in [1, 2^30]")
+    x = x.reshape(-1)
+    n = x.numel()
+    if n < 1:
+        raise ValueError("cannot quantise an empty array")
+    ws = _quant_ws(workspace, x.device, int(_lib.lib().dpz_quant_workspace_bytes(n)))
+    info_dev = torch.empty(8, dtype=torch.int32, device=x.device)
+    # norm = fl(max / k) keeps max / norm within a few ulp of k: two bits above k's length,
+    # except where norm is subnormal (status 4: once more with the full 32 bits)
+    for w_cap in (min(32, k.bit_length() + 2), 32):
+        cap = 4 * ((n * w_cap + 31) // 32)
+        body = torch.empty(cap, dtype=torch.uint8, device=x.device)
+        rc = _lib.lib().dpz_quant_encode(_ptr(x), n, k, _ptr(body), cap, _ptr(info_dev),
+                                         _ptr(ws), ws.numel(), _stream(x.device))
+        check(rc, "dpz_quant_encode")
+        info = QuantInfo(info_dev.cpu().numpy())
+        if info.status != 4:
+            break
+    if info.status == 1:
+        raise ValueError("cannot quantise an all-zero array")
+    if info.status == 2:
+        raise ValueError("cannot quantise a non-finite array")
+    if info.status != 0:
+        raise ValueError("cannot quantise: max|x| / float_precision underflows")
+    return body[:(n * info.w + 7) // 8], info
+
+
+def quant_decode(body, n, w, scale, out=None):
+    """Values of a quantised stream body held on the device (a uint8 tensor, 4-byte aligned,
+    readable up to the next multiple of 4 bytes): ``float32(float64(u - 2^(w-1) + 1) * scale)``
+    (compression/Quantization.py:93-132).  ``n``, ``w`` and ``scale`` come from the stream's
+    header; nothing synchronises."""
+    _require(body, torch.uint8, "body")
+    n, w = int(n), int(w)
+    if n < 1 or not 2 <= w <= 32 or 8 * body.numel() < n * w:
+        raise ValueError("malformed quantised stream")
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=body.device)
+    _require(out, torch.float32, "out")
+    if out.numel() < n:
+        raise ValueError("out holds fewer than n values")
+    nbytes = (n * w + 7) // 8
+    store = body.untyped_storage()
+    if body.storage_offset() + ((nbytes + 3) // 4) * 4 > store.nbytes():
+        raise ValueError("body must be readable up to the next multiple of 4 bytes")
+    rc = _lib.lib().dpz_quant_decode(_ptr(body), nbytes, n, w, float(scale), _ptr(out),
+                                     _stream(body.device))
+    if rc == _lib.DPZ_ERR_ARG:
+        raise ValueError("malformed quantised stream")
+    check(rc, "dpz_quant_decode")
+    return out[:n]
 
 
 class KernelTimer:

@@ -533,7 +533,8 @@ enum {
   DPZ_KT_ELIAS_SCAN, DPZ_KT_ELIAS_PACK, DPZ_KT_ELIAS_SPEC, DPZ_KT_ELIAS_RESOLVE,
   DPZ_KT_ELIAS_WRITE, DPZ_KT_FP16, DPZ_KT_SCATTER, DPZ_KT_FPZ_SIZE, DPZ_KT_FPZ_SCAN,
   DPZ_KT_FPZ_PACK, DPZ_KT_FPZ_DECODE, DPZ_KT_CPLX, DPZ_KT_FFT_SCALE, DPZ_KT_HAAR, DPZ_KT_LZ4,
-  DPZ_KT_COUNTER, DPZ_KT_FFT, DPZ_KT_COUNT
+  DPZ_KT_COUNTER, DPZ_KT_FFT, DPZ_KT_QUANT_STATS, DPZ_KT_QUANT_PACK, DPZ_KT_QUANT_UNPACK,
+  DPZ_KT_COUNT
 };
 int dpz_timing_enable(int on);  /* also clears the accumulators */
 int dpz_timing_read(double* ms_sum, int64_t* count, int max_ids);
@@ -719,6 +720,38 @@ int dpz_mask_decode_average(const float* local, int64_t n, int n_payloads,
                             const uint32_t* const* mask, const int32_t* const* rank_tab,
                             const float* const* vals, const float* w, float w_self, int flags,
                             float* out, dpz_stream_t stream);
+
+/* ---- Quantization (reference compression/Quantization.py), bit for bit ------------------------
+ * Encode of n fp32 values x with float_precision k (1 <= k <= 2^30), all in fp32 with IEEE
+ * divisions and ties-to-even rounding:
+ *   m = max|x|,  S = the fp32 sum of |x| in numpy's order (consecutive chunks of 8192 elements,
+ *   numpy's pairwise tree inside a chunk, the chunk sums added one after another),
+ *   scale = (S / n) / k,  norm = m / k,  q_i = int32(rint(x_i / norm)),  qmax = |rint(m / norm)|,
+ *   p = the power of two above qmax,  w = log2(p) + 1 bits per value,  u_i = q_i + p - 1.
+ * Body: stream bit i*w + j holds bit w-1-j of u_i; stream bit t is bit t & 7 of byte t >> 3;
+ * unused trailing bits are 0.  The wire value the Python class sends is
+ * pickle((scale, uint8[padding, w, body...])) with padding = (8 - n*w % 8) % 8.
+ * The reference rescales by the mean although it normalised by the max, so amplitudes do not
+ * round-trip; the scale travels in the stream.
+ * A statistics kernel and a pack kernel run back to back on `stream`, with no
+ * host synchronisation; the pack kernel derives the parameters on the device and writes them to
+ * `info`, 8 int32 words on the DEVICE:
+ *   [0] status: 0 ok, 1 max|x| == 0, 2 a non-finite value, 3 m / k underflows, 4 body_cap too
+ *       small for the width found (nothing is written to body for status != 0),
+ *   [1] w, [2] padding, [3] scale bits, [4] norm bits, [5] max|x| bits, [6] S bits, [7] p - 1.
+ * body: 4-byte aligned, body_cap bytes (a multiple of 4, at least 4 * ceil(n * w / 32); the words
+ * past ceil(n*w/8) bytes are zero padding).  ws: dpz_quant_workspace_bytes(n), 16-byte aligned.
+ * dpz_quant_block_elems(): the values one block of the pack kernel covers.
+ * dpz_quant_decode: out[i] = float(double(u_i - 2^(w-1) + 1) * scale) for the n values of a body of
+ * body_bytes bytes held in a 4-byte aligned DEVICE buffer readable up to the next multiple of 4.
+ * Both return DPZ_ERR_ARG before any device call for n < 1 (or n >= 2^31), k outside [1, 2^30],
+ * w outside [2, 32], a body shorter than n * w bits, null or misaligned pointers.            */
+size_t dpz_quant_workspace_bytes(int64_t n);
+int64_t dpz_quant_block_elems(void);
+int dpz_quant_encode(const float* x, int64_t n, int64_t k, uint8_t* body, int64_t body_cap,
+                     int32_t* info, void* ws, size_t ws_bytes, dpz_stream_t stream);
+int dpz_quant_decode(const uint8_t* body, int64_t body_bytes, int64_t n, int w, double scale,
+                     float* out, dpz_stream_t stream);
 
 #ifdef __cplusplus
 }
