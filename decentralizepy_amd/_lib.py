@@ -218,6 +218,13 @@ SIGNATURES = {
                                        ctypes.POINTER(_c_void_p), ctypes.POINTER(_c_void_p),
                                        ctypes.POINTER(ctypes.c_float), ctypes.c_float, _int,
                                        _c_void_p, _c_void_p]),
+    "dpz_mt_mask_batch_workspace_bytes": (_size, [_int, _i64]),
+    "dpz_mt_mask_batch": (_int, [_int, ctypes.POINTER(ctypes.c_uint32),
+                                 ctypes.POINTER(ctypes.c_float), _i64, _c_void_p, _i64, _c_void_p,
+                                 _i64, _c_void_p, _c_void_p, _size, _c_void_p]),
+    "dpz_mask_gather_nodes": (_int, [_int, _c_void_p, _i64, _i64, _c_void_p]),
+    "dpz_mask_decode_average_nodes": (_int, [_int, _c_void_p, ctypes.POINTER(_int), _i64, _int,
+                                             _c_void_p, _i64, _c_void_p]),
     "dpz_quant_workspace_bytes": (_size, [_i64]),
     "dpz_quant_block_elems": (_i64, []),
     "dpz_quant_encode": (_int, [_c_void_p, _i64, _i64, _c_void_p, _i64, _c_void_p, _c_void_p,

@@ -24,7 +24,9 @@ __all__ = ["DPZ_ACC_NONE", "DPZ_ACC_ACCUMULATE", "DPZ_ACC_ADD", "DPZ_EW_SUB", "D
            "cplx_gather", "cplx_pair_indices", "lz4_compress", "lz4_decompress", "lz4_frame_info",
            "delta_i32", "running_sum_i32", "mask_words", "topk_encode_sliced", "counter_unslice",
            "counter_slice", "rewind_apply", "counter_flush", "counter_flush_batch", "mt_mask",
-           "mt_rank_entries", "mask_gather", "mask_decode_average", "quant_encode", "quant_decode",
+           "mt_rank_entries", "mask_gather", "mask_decode_average", "mt_mask_batch",
+           "gather_node_table", "mask_gather_nodes", "fold_node_table",
+           "mask_decode_average_nodes", "quant_encode", "quant_decode",
            "quant_block_elems", "QuantInfo"]
 
 
@@ -1271,6 +1273,115 @@ def mask_decode_average(local, payloads, weights, w_self=None, out=None, counts=
             _stream(local.device))
         check(rc, "dpz_mask_decode_average")
     return out
+
+
+def mt_mask_batch(seeds, alphas, n, device, mask=None, rank_tab=None, count=None,
+                  workspace=None):
+    """``mt_mask`` for ``len(seeds)`` masks of one length with one launch per phase
+    (dpz_mt_mask_batch): row i of the returned ``(mask int32[m, >= mask_words(n)], rank_tab
+    int32[m, >= mt_rank_entries(n)], count int64[m])`` is bit for bit ``mt_mask(seeds[i],
+    alphas[i], n)``.  Caller-owned outputs are 2-D with contiguous rows; a mask row stride is a
+    multiple of 4 words.  Nothing blocks (but the first call on a device, as ``mt_mask``)."""
+    n, m = int(n), len(seeds)
+    if m < 1 or len(alphas) != m:
+        raise ValueError("seeds and alphas must hold one entry per mask, at least one")
+    device = torch.device(device)
+    if mask is None:
+        mask = torch.empty(m, -(-mask_words(n) // 4) * 4, dtype=torch.int32, device=device)
+    if rank_tab is None:
+        rank_tab = torch.empty(m, mt_rank_entries(n), dtype=torch.int32, device=device)
+    if count is None:
+        count = torch.empty(m, dtype=torch.int64, device=device)
+    for t, dtype, name, need in ((mask, torch.int32, "mask", mask_words(n)),
+                                 (rank_tab, torch.int32, "rank_tab", mt_rank_entries(n))):
+        if not t.is_cuda or t.dtype != dtype or t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f"{name} must be a 2-D {dtype} device tensor with contiguous rows")
+        if t.shape[0] < m or t.shape[1] < need or (m > 1 and t.stride(0) < need):
+            raise ValueError(f"{name} too small for {m} masks of {n} elements")
+    _require(count, torch.int64, "count")
+    if count.numel() < m:
+        raise ValueError("count must hold one word per mask")
+    L = _lib.lib()
+    ws = _mt_ws(workspace, device, int(L.dpz_mt_mask_batch_workspace_bytes(m, n)))
+    s_arr = (ctypes.c_uint32 * m)(*[int(s) & 0xffffffff for s in seeds])
+    a_arr = (ctypes.c_float * m)(*[float(np.float32(a)) for a in alphas])
+    with torch.cuda.device(device):  # the jump tables are kept per device
+        rc = L.dpz_mt_mask_batch(m, s_arr, a_arr, n, _ptr(mask), mask.stride(0), _ptr(rank_tab),
+                                 rank_tab.stride(0), _ptr(count), _ptr(ws), ws.numel(),
+                                 _stream(device))
+    check(rc, "dpz_mt_mask_batch")
+    return mask, rank_tab, count
+
+
+def _row_ptrs(rows, m):
+    """Device addresses of m rows: the rows of a 2-D tensor or the words of a 1-D one (computed
+    from its stride, no views), or a list's tensors."""
+    if rows is None:
+        return [0] * m
+    if isinstance(rows, torch.Tensor):
+        step = rows.stride(0) * rows.element_size()
+        return [rows.data_ptr() + j * step for j in range(m)]
+    return [t.data_ptr() for t in rows]
+
+
+def gather_node_table(x, mask, rank_tab, vals, count, status, counter=None):
+    """The DEVICE node table of ``mask_gather_nodes``: 8 64-bit words per node {x, mask, rank_tab,
+    vals, counter or 0, count, status, 0}.  Every argument is a 2-D tensor (one row per node) or
+    a list of per-node tensors; ``count`` (int64) and ``status`` (int32) are 1-D (any stride), one
+    word per node."""
+    m = x.shape[0] if isinstance(x, torch.Tensor) else len(x)
+    dev = (x if isinstance(x, torch.Tensor) else x[0]).device
+    cols = [_row_ptrs(t, m) for t in (x, mask, rank_tab, vals, counter)]
+    cols += [_row_ptrs(count, m), _row_ptrs(status, m), [0] * m]
+    tab = np.array(cols, dtype=np.uint64).T.copy()
+    return torch.from_numpy(tab.view(np.int64)).to(dev)
+
+
+def mask_gather_nodes(table, n, cap):
+    """``mask_gather`` of every node of ``table`` (``gather_node_table``) in one launch, each into
+    its slot of ``cap`` values: a node whose mask selects more leaves its slot filled up to
+    ``cap``, nothing past it, and its status word nonzero (zero otherwise)."""
+    _require(table, torch.int64, "table")
+    rc = _lib.lib().dpz_mask_gather_nodes(table.shape[0], _ptr(table), int(n), int(cap),
+                                          _stream(table.device))
+    check(rc, "dpz_mask_gather_nodes")
+
+
+def fold_node_table(dests, device):
+    """The DEVICE fold table of ``mask_decode_average_nodes`` and the host copy of its payload
+    counts.  ``dests``: per destination ``(local, out, w_self or None, [(mask, rank_tab, vals,
+    w), ...])`` with 1..16 payloads; 68 64-bit words each: {local, out, w_self, n_payloads}, then
+    {mask, rank_tab, vals, w} per payload (weights as fp32 bits in the low half of their word)."""
+    def f32(v):
+        return int(np.float32(v).view(np.uint32))
+
+    tab = np.zeros((max(1, len(dests)), 4 + 4 * MASK_FOLD_MAX), dtype=np.uint64)
+    counts = (ctypes.c_int * max(1, len(dests)))()
+    for j, (local, out, w_self, pays) in enumerate(dests):
+        counts[j] = len(pays)
+        tab[j, :4] = (local.data_ptr(), out.data_ptr(), f32(w_self or 0.0), len(pays))
+        for p, (mask, rank_tab, vals, w) in enumerate(pays[:MASK_FOLD_MAX]):
+            if vals.numel() == 0:  # an empty selection: never read, but kept a valid address
+                vals = local
+            tab[j, 4 + 4 * p:8 + 4 * p] = (mask.data_ptr(), rank_tab.data_ptr(), vals.data_ptr(),
+                                           f32(w))
+    return torch.from_numpy(tab.view(np.int64)).to(device), counts
+
+
+def mask_decode_average_nodes(table, counts, n, self_term=True, guard=None):
+    """``mask_decode_average`` of every destination of ``table`` (``fold_node_table``) in one
+    launch.  ``guard`` (int32 device words, e.g. the gathers' status words): nothing is written
+    if any is nonzero.  Returns False, with nothing enqueued, when a destination has more than
+    16 payloads (the caller folds that round through ``mask_decode_average``)."""
+    _require(table, torch.int64, "table")
+    _require(guard, torch.int32, "guard")
+    rc = _lib.lib().dpz_mask_decode_average_nodes(
+        len(counts), _ptr(table), counts, int(n), DPZ_FOLD_SELF if self_term else 0, _ptr(guard),
+        guard.numel() if guard is not None else 0, _stream(table.device))
+    if rc == _lib.DPZ_ERR_UNSUPPORTED and max(counts) > MASK_FOLD_MAX:
+        return False
+    check(rc, "dpz_mask_decode_average_nodes")
+    return True
 
 
 class QuantInfo:

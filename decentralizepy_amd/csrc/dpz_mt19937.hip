@@ -126,8 +126,8 @@ __device__ __forceinline__ void init_state(uint32_t seed, uint32_t* st) {
 }
 
 // coarse launch: block d - 1 writes the state in front of element d * COARSE * CHUNK
-__global__ void __launch_bounds__(THREADS)
-mt_coarse_kernel(uint32_t seed, const uint32_t* __restrict__ coarse, uint32_t* __restrict__ states) {
+__device__ __forceinline__ void coarse_body(uint32_t seed, const uint32_t* __restrict__ coarse,
+                                            uint32_t* __restrict__ states) {
   __shared__ uint32_t winbuf[WIN_WORDS];
   uint32_t* win = winbuf + WIN_FRONT;
   const int d = blockIdx.x + 1;
@@ -136,12 +136,32 @@ mt_coarse_kernel(uint32_t seed, const uint32_t* __restrict__ coarse, uint32_t* _
   if (threadIdx.x < N) states[(size_t)d * N + threadIdx.x] = win[threadIdx.x];
 }
 
+__global__ void __launch_bounds__(THREADS)
+mt_coarse_kernel(uint32_t seed, const uint32_t* __restrict__ coarse, uint32_t* __restrict__ states) {
+  coarse_body(seed, coarse, states);
+}
+
+// the seeds and thresholds of one launch group of a batch, by value (as FoldArgs' payloads)
+constexpr int MASK_GROUP = 64;
+struct MaskBatchArgs {
+  uint32_t seed[MASK_GROUP];
+  int32_t thr[MASK_GROUP];
+};
+
+// batch: blockIdx.y is the mask; its states are row blockIdx.y of `states`
+__global__ void __launch_bounds__(THREADS)
+mt_coarse_batch_kernel(MaskBatchArgs a, const uint32_t* __restrict__ coarse,
+                       uint32_t* __restrict__ states, int64_t states_stride) {
+  coarse_body(a.seed[blockIdx.y], coarse, states + blockIdx.y * states_stride);
+}
+
 // one block per chunk: jump to the chunk's first element, regenerate the state ceil(len / 624)
 // times, temper, compare, pack the chunk's mask words and its per-group exclusive popcounts
-__global__ void __launch_bounds__(THREADS)
-mt_mask_kernel(uint32_t seed, int32_t thr, int64_t n, const uint32_t* __restrict__ fine,
-               const uint32_t* __restrict__ states, uint32_t* __restrict__ mask,
-               int32_t* __restrict__ rank_tab) {
+__device__ __forceinline__ void mask_body(uint32_t seed, int32_t thr, int64_t n,
+                                          const uint32_t* __restrict__ fine,
+                                          const uint32_t* __restrict__ states,
+                                          uint32_t* __restrict__ mask,
+                                          int32_t* __restrict__ rank_tab) {
   __shared__ uint32_t winbuf[WIN_WORDS];
   uint32_t* win = winbuf + WIN_FRONT;
   __shared__ uint32_t bits[CHUNK_WORDS + BITS_PAD];
@@ -201,9 +221,27 @@ mt_mask_kernel(uint32_t seed, int32_t thr, int64_t n, const uint32_t* __restrict
   if (tid == 0) rank_tab[G + chunk] = (int32_t)total;  // made exclusive by mt_scan_kernel
 }
 
+__global__ void __launch_bounds__(THREADS)
+mt_mask_kernel(uint32_t seed, int32_t thr, int64_t n, const uint32_t* __restrict__ fine,
+               const uint32_t* __restrict__ states, uint32_t* __restrict__ mask,
+               int32_t* __restrict__ rank_tab) {
+  mask_body(seed, thr, n, fine, states, mask, rank_tab);
+}
+
+// batch: a grid of chunks x masks, blockIdx.y the mask (row blockIdx.y of every output)
+__global__ void __launch_bounds__(THREADS)
+mt_mask_batch_kernel(MaskBatchArgs a, int64_t n, const uint32_t* __restrict__ fine,
+                     const uint32_t* __restrict__ states, int64_t states_stride,
+                     uint32_t* __restrict__ mask, int64_t mask_stride,
+                     int32_t* __restrict__ rank_tab, int64_t rank_stride) {
+  const int64_t i = blockIdx.y;
+  mask_body(a.seed[i], a.thr[i], n, fine, states + i * states_stride, mask + i * mask_stride,
+            rank_tab + i * rank_stride);
+}
+
 // rank_tab[G + c]: chunk totals -> exclusive prefix, in place; *count = the number selected
-__global__ void __launch_bounds__(1024)
-mt_scan_kernel(int32_t* __restrict__ chunk_tab, int chunks, int64_t* __restrict__ count) {
+__device__ __forceinline__ void scan_body(int32_t* __restrict__ chunk_tab, int chunks,
+                                          int64_t* __restrict__ count) {
   __shared__ uint32_t wsum[16];
   uint32_t carry = 0;
   for (int b = 0; b < chunks; b += 1024) {
@@ -215,6 +253,18 @@ mt_scan_kernel(int32_t* __restrict__ chunk_tab, int chunks, int64_t* __restrict_
     carry += total;
   }
   if (threadIdx.x == 0) *count = (int64_t)carry;
+}
+
+__global__ void __launch_bounds__(1024)
+mt_scan_kernel(int32_t* __restrict__ chunk_tab, int chunks, int64_t* __restrict__ count) {
+  scan_body(chunk_tab, chunks, count);
+}
+
+// batch: one block per mask
+__global__ void __launch_bounds__(1024)
+mt_scan_batch_kernel(int32_t* __restrict__ rank_tab, int64_t rank_stride, int64_t G, int chunks,
+                     int64_t* __restrict__ count) {
+  scan_body(rank_tab + blockIdx.x * rank_stride + G, chunks, count + blockIdx.x);
 }
 
 // ---- consumers: four consecutive elements per thread -------------------------------------------
@@ -319,6 +369,120 @@ mask_fold_kernel(const float* __restrict__ local, int64_t n, FoldArgs a, float* 
   }
 }
 
+// ---- a round's nodes in one launch: blockIdx.y is the node / the destination -----------------
+// node table of dpz_mask_gather_nodes: 8 64-bit words per node
+struct GatherNode {
+  const float* x;
+  const uint32_t* mask;
+  const int32_t* rank_tab;
+  float* vals;
+  int32_t* counter;  // or null
+  const int64_t* count;
+  int32_t* status;
+  uint64_t pad;
+};
+static_assert(sizeof(GatherNode) == 64, "8 64-bit words");
+
+// mask_gather_kernel into a slot of `cap` values: a selected element whose rank is past the slot
+// is not written (its counter still is), and the node's status word says so
+__global__ void __launch_bounds__(256)
+mask_gather_nodes_kernel(const GatherNode* __restrict__ tab, int64_t n, int64_t cap) {
+  const GatherNode nd = tab[blockIdx.y];
+  const int64_t q = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (q == 0) *nd.status = *nd.count > cap ? 1 : 0;
+  if (q >= n) return;
+  int32_t rank = 0;
+  const uint32_t nib = quad_bits(nd.mask, nd.rank_tab, q, (n + 31) >> 5, n_groups(n), &rank);
+  if (!nib) return;
+  float v[4];
+  if (aligned16(nd.x) && q + 4 <= n) {  // per row: packed rows of an n that is no multiple of 4
+    const float4 t = *reinterpret_cast<const float4*>(nd.x + q);
+    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = q + i < n ? nd.x[q + i] : 0.0f;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if ((nib >> i) & 1u) {
+      if (rank < cap) nd.vals[rank] = v[i];
+      ++rank;
+      if (nd.counter) nd.counter[q + i] += 1;
+    }
+  }
+}
+
+// fold table of dpz_mask_decode_average_nodes: 68 64-bit words per destination
+struct FoldPayload {
+  const uint32_t* mask;
+  const int32_t* rank_tab;
+  const float* vals;
+  float w;
+  uint32_t pad;
+};
+struct FoldDest {
+  const float* local;
+  float* out;
+  float w_self;
+  uint32_t pad0;
+  int64_t np;
+  FoldPayload p[MAX_PAYLOADS];
+};
+static_assert(sizeof(FoldDest) == 8 * (4 + 4 * MAX_PAYLOADS), "68 64-bit words");
+
+// mask_fold_kernel (no running total) for every destination of a round, behind the guard words
+__global__ void __launch_bounds__(256)
+mask_fold_nodes_kernel(const FoldDest* __restrict__ tab, int64_t n, int self,
+                       const int32_t* __restrict__ guard, int64_t guard_n) {
+  if (guard) {  // a gather that overflowed its slot: no fold of this launch writes
+    const int lane = threadIdx.x & 63;
+    bool bad = false;
+    for (int64_t i = lane; i < guard_n; i += 64) bad |= guard[i] != 0;
+    if (__ballot(bad) != 0) return;  // every wave reads the same final words
+  }
+  const FoldDest* __restrict__ d = tab + blockIdx.y;
+  const int64_t q = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (q >= n) return;
+  const float* __restrict__ local = d->local;
+  float* out = d->out;
+  const int np = (int)min(d->np, (int64_t)MAX_PAYLOADS);  // the host checked its own copy
+  const int64_t words = (n + 31) >> 5, G = n_groups(n);
+  const bool full = aligned16(local) && aligned16(out) && q + 4 <= n;
+  float x[4], t[4];
+  if (full) {
+    const float4 l = *reinterpret_cast<const float4*>(local + q);
+    x[0] = l.x, x[1] = l.y, x[2] = l.z, x[3] = l.w;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) x[i] = q + i < n ? local[q + i] : 0.0f;
+  }
+  for (int p = 0; p < np; ++p) {  // uniform over the block: one destination per blockIdx.y
+    int32_t rank = 0;
+    const uint32_t nib = quad_bits(d->p[p].mask, d->p[p].rank_tab, q, words, G, &rank);
+    const float w = d->p[p].w;
+    const float* __restrict__ vals = d->p[p].vals;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float v = x[i];
+      if ((nib >> i) & 1u) v = vals[rank++];
+      const float term = w * v;
+      t[i] = p ? t[i] + term : term;
+    }
+  }
+  if (self) {
+    const float ws = d->w_self;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) t[i] = t[i] + ws * x[i];
+  }
+  if (full) {
+    *reinterpret_cast<float4*>(out + q) = make_float4(t[0], t[1], t[2], t[3]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (q + i < n) out[q + i] = t[i];
+  }
+}
+
 static size_t states_bytes(int64_t n) {
   const int64_t coarse = (n_chunks(n) + COARSE - 1) / COARSE;  // coarse steps, the first at 0
   return coarse > 1 ? (size_t)coarse * N * sizeof(uint32_t) : 0;
@@ -361,6 +525,83 @@ int dpz_mt_mask(uint32_t seed, float alpha, int64_t n, uint32_t* mask, int32_t* 
                                                         states, mask, rank_tab);
   DPZ_LAUNCH_CHECK();
   mt_scan_kernel<<<1, 1024, 0, st>>>(rank_tab + n_groups(n), (int)chunks, count_dev);
+  DPZ_LAUNCH_CHECK();
+  return DPZ_OK;
+}
+
+size_t dpz_mt_mask_batch_workspace_bytes(int m, int64_t n) {
+  if (m < 1 || n < 1 || n >= MAX_ELEMS) return 0;
+  return (size_t)m * states_bytes(n) + 256;
+}
+
+int dpz_mt_mask_batch(int m, const uint32_t* seeds, const float* alphas, int64_t n, uint32_t* mask,
+                      int64_t mask_stride, int32_t* rank_tab, int64_t rank_stride,
+                      int64_t* count_dev, void* ws, size_t ws_bytes, dpz_stream_t stream) {
+  if (m < 1 || n < 1 || !seeds || !alphas || !mask || !rank_tab || !count_dev || !ws)
+    return DPZ_ERR_ARG;
+  if (n >= MAX_ELEMS) return DPZ_ERR_UNSUPPORTED;
+  if (mask_stride < ((n + 31) >> 5) || (mask_stride & 3) ||
+      rank_stride < n_groups(n) + n_chunks(n))
+    return DPZ_ERR_ARG;
+  if (ws_bytes < dpz_mt_mask_batch_workspace_bytes(m, n)) return DPZ_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t chunks = n_chunks(n);
+  const int coarse = (int)((chunks + COARSE - 1) / COARSE);
+  DevTables tab;
+  const int rc = device_tables((int)(chunks < COARSE ? chunks : COARSE), coarse, &tab);
+  if (rc != DPZ_OK) return rc;
+  uint32_t* states = reinterpret_cast<uint32_t*>(ws);  // mask i: rows [i * coarse, (i + 1) * coarse)
+  const int64_t states_stride = coarse > 1 ? (int64_t)coarse * N : 0;
+  for (int g0 = 0; g0 < m; g0 += MASK_GROUP) {  // one launch per MASK_GROUP masks: m <= 64, one
+    const int gm = m - g0 < MASK_GROUP ? m - g0 : MASK_GROUP;
+    MaskBatchArgs a;
+    for (int i = 0; i < MASK_GROUP; ++i) {
+      a.seed[i] = i < gm ? seeds[g0 + i] : 0u;
+      a.thr[i] = i < gm ? mask_threshold(alphas[g0 + i]) : -1;
+    }
+    uint32_t* gs = states + g0 * states_stride;
+    if (coarse > 1) {
+      mt_coarse_batch_kernel<<<dim3((unsigned)(coarse - 1), (unsigned)gm), THREADS, 0, st>>>(
+          a, tab.coarse, gs, states_stride);
+      DPZ_LAUNCH_CHECK();
+    }
+    mt_mask_batch_kernel<<<dim3((unsigned)chunks, (unsigned)gm), THREADS, 0, st>>>(
+        a, n, tab.fine, gs, states_stride, mask + g0 * mask_stride, mask_stride,
+        rank_tab + g0 * rank_stride, rank_stride);
+    DPZ_LAUNCH_CHECK();
+  }
+  mt_scan_batch_kernel<<<(unsigned)m, 1024, 0, st>>>(rank_tab, rank_stride, n_groups(n),
+                                                     (int)chunks, count_dev);
+  DPZ_LAUNCH_CHECK();
+  return DPZ_OK;
+}
+
+int dpz_mask_gather_nodes(int m, const void* node_table, int64_t n, int64_t cap,
+                          dpz_stream_t stream) {
+  if (m < 1 || n < 1 || cap < 1 || !node_table) return DPZ_ERR_ARG;
+  if (n >= MAX_ELEMS || m > 65535) return DPZ_ERR_UNSUPPORTED;
+  const int64_t blocks = ((n + 3) / 4 + 255) / 256;
+  mask_gather_nodes_kernel<<<dim3((unsigned)blocks, (unsigned)m), 256, 0, (hipStream_t)stream>>>(
+      reinterpret_cast<const GatherNode*>(node_table), n, cap);
+  DPZ_LAUNCH_CHECK();
+  return DPZ_OK;
+}
+
+int dpz_mask_decode_average_nodes(int m, const void* fold_table, const int* n_payloads, int64_t n,
+                                  int flags, const int32_t* guard, int64_t guard_n,
+                                  dpz_stream_t stream) {
+  if (m < 1 || n < 1 || !fold_table || !n_payloads || guard_n < 0 || (!guard && guard_n))
+    return DPZ_ERR_ARG;
+  if (flags & ~DPZ_FOLD_SELF) return DPZ_ERR_ARG;
+  for (int j = 0; j < m; ++j)
+    if (n_payloads[j] < 1) return DPZ_ERR_ARG;
+  if (n >= MAX_ELEMS || m > 65535) return DPZ_ERR_UNSUPPORTED;
+  for (int j = 0; j < m; ++j)
+    if (n_payloads[j] > MAX_PAYLOADS) return DPZ_ERR_UNSUPPORTED;
+  const int64_t blocks = ((n + 3) / 4 + 255) / 256;
+  mask_fold_nodes_kernel<<<dim3((unsigned)blocks, (unsigned)m), 256, 0, (hipStream_t)stream>>>(
+      reinterpret_cast<const FoldDest*>(fold_table), n, (flags & DPZ_FOLD_SELF) ? 1 : 0,
+      guard_n ? guard : nullptr, guard_n);
   DPZ_LAUNCH_CHECK();
   return DPZ_OK;
 }

@@ -721,6 +721,45 @@ int dpz_mask_decode_average(const float* local, int64_t n, int n_payloads,
                             const float* const* vals, const float* w, float w_self, int flags,
                             float* out, dpz_stream_t stream);
 
+/* ---- SubSampling, a round's nodes at once (decentralizepy_amd/gossip_subsampling.py) -----------
+ * The three calls above for m nodes with one launch per phase, the node in the grid's second
+ * dimension: the masks of different nodes are independent and share the jump tables, and one
+ * mask alone leaves most of the machine idle (n / 65536 blocks).  All three validate before any
+ * device call: DPZ_ERR_ARG for m < 1, n < 1, null pointers or bad strides, DPZ_ERR_UNSUPPORTED
+ * for n >= 2^31, DPZ_ERR_WORKSPACE for a short workspace.
+ * dpz_mt_mask_batch: m masks of one length n; mask i from seeds[i] / alphas[i] (HOST arrays,
+ * handed to the kernels by value, 64 masks per launch group; no copy, no synchronisation).  Row i
+ * of mask (mask_stride words apart, a multiple of 4 and >= dpz_mask_words(n)), of rank_tab
+ * (rank_stride entries apart, >= dpz_mt_rank_entries(n)) and count_dev[i] are bit for bit what
+ * dpz_mt_mask(seeds[i], alphas[i], n, ...) writes.  One mask launch over chunks x m blocks, one
+ * scan launch over m blocks and, above dpz_mt_coarse_chunks() chunks, one coarse launch over
+ * (coarse - 1) x m blocks.  ws: dpz_mt_mask_batch_workspace_bytes(m, n).  Like dpz_mt_mask, a
+ * call that needs table rows its device does not have yet BLOCKS on the host build and copy.
+ * dpz_mask_gather_nodes: node_table is a DEVICE array of m entries of 8 64-bit words {x, mask,
+ * rank_tab, vals, counter (or 0), count, status, 0}: count the mask's DEVICE int64 count, vals a
+ * slot of `cap` values, status a DEVICE int32.  vals[rank(j)] = x[j] for every selected j with
+ * rank(j) < cap, counter[j] += 1 for every selected j; nothing is written at or past vals + cap,
+ * and status = (*count > cap) ? 1 : 0, so a slot that was too small is reported, never silently
+ * truncated.  The float4 read of x is chosen per row from the row's alignment.
+ * dpz_mask_decode_average_nodes: fold_table is a DEVICE array of m destinations of 68 64-bit
+ * words: {local, out, w_self (fp32 in the low half), n_payloads} and 16 entries {mask, rank_tab,
+ * vals, w (fp32 in the low half)}, the first n_payloads used; n_payloads (HOST int[m]) repeats the
+ * counts so that a destination with more than 16 payloads is refused (DPZ_ERR_UNSUPPORTED, nothing
+ * enqueued: the caller folds it through dpz_mask_decode_average with DPZ_FOLD_ACCUMULATE).  Each
+ * element is folded exactly as by dpz_mask_decode_average; flags: DPZ_FOLD_SELF or 0.  The
+ * launch first reads guard[0, guard_n) (DEVICE int32, may be NULL with guard_n = 0, e.g. the
+ * gather's status words) and writes nothing if any word is nonzero.  No out may overlap any
+ * local.                                                                                        */
+size_t dpz_mt_mask_batch_workspace_bytes(int m, int64_t n);
+int dpz_mt_mask_batch(int m, const uint32_t* seeds, const float* alphas, int64_t n, uint32_t* mask,
+                      int64_t mask_stride, int32_t* rank_tab, int64_t rank_stride,
+                      int64_t* count_dev, void* ws, size_t ws_bytes, dpz_stream_t stream);
+int dpz_mask_gather_nodes(int m, const void* node_table, int64_t n, int64_t cap,
+                          dpz_stream_t stream);
+int dpz_mask_decode_average_nodes(int m, const void* fold_table, const int* n_payloads, int64_t n,
+                                  int flags, const int32_t* guard, int64_t guard_n,
+                                  dpz_stream_t stream);
+
 /* ---- Quantization (reference compression/Quantization.py), bit for bit ------------------------
  * Encode of n fp32 values x with float_precision k (1 <= k <= 2^30), all in fp32 with IEEE
  * divisions and ties-to-even rounding:
