@@ -47,6 +47,9 @@ DPZ_COUNTER_AUTO = 0
 DPZ_COUNTER_SCATTER = 1
 DPZ_COUNTER_SWEEP = 2
 DPZ_COUNTER_SPARSE = 3
+DPZ_DENSE_AUTO = 0
+DPZ_DENSE_STAGED = 1
+DPZ_DENSE_DIRECT = 2
 DPZ_OK = 0
 DPZ_ERR_ARG = 1001
 DPZ_ERR_WORKSPACE = 1002
@@ -231,6 +234,10 @@ SIGNATURES = {
                                 _size, _c_void_p]),
     "dpz_quant_decode": (_int, [_c_void_p, _i64, _i64, _int, ctypes.c_double, _c_void_p,
                                 _c_void_p]),
+    "dpz_dense_tile_elems": (_i64, [_int]),
+    "dpz_dense_auto_mode": (_int, [_int, _i64, _i64]),
+    "dpz_dense_average_nodes": (_int, [_int, _c_void_p, _c_void_p, _i64, _int, _i64, _int,
+                                       _c_void_p]),
 }
 
 _lib = None

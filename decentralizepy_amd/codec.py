@@ -27,7 +27,8 @@ __all__ = ["DPZ_ACC_NONE", "DPZ_ACC_ACCUMULATE", "DPZ_ACC_ADD", "DPZ_EW_SUB", "D
            "mt_rank_entries", "mask_gather", "mask_decode_average", "mt_mask_batch",
            "gather_node_table", "mask_gather_nodes", "fold_node_table",
            "mask_decode_average_nodes", "quant_encode", "quant_decode",
-           "quant_block_elems", "QuantInfo"]
+           "quant_block_elems", "QuantInfo", "dense_tile_elems", "dense_auto_mode", "DenseTable",
+           "dense_average_nodes"]
 
 
 def _ptr(t):
@@ -1382,6 +1383,63 @@ def mask_decode_average_nodes(table, counts, n, self_term=True, guard=None):
         return False
     check(rc, "dpz_mask_decode_average_nodes")
     return True
+
+
+def dense_tile_elems(n_src):
+    """The column tile of the staged dense fold for ``n_src`` source rows: the largest of 1024 /
+    512 / 256 elements whose rows fit 64 KiB of LDS; 0 when none does (only the direct path)."""
+    return int(_lib.lib().dpz_dense_tile_elems(int(n_src)))
+
+
+def dense_auto_mode(n_src, row_reads, n):
+    """The path DPZ_DENSE_AUTO takes for ``n_src`` sources, ``row_reads`` = sum(count + 1) over
+    the receivers and rows of n elements: DPZ_DENSE_STAGED or DPZ_DENSE_DIRECT."""
+    return int(_lib.lib().dpz_dense_auto_mode(int(n_src), int(row_reads), int(n)))
+
+
+class DenseTable:
+    """The fold table of ``dense_average_nodes``: the DEVICE words and the host copy the library
+    validates (kept alive here), with the counts the call repeats."""
+
+    def __init__(self, srcs, recvs, device):
+        """srcs: the source rows (a 2-D tensor or a list of 1-D tensors); recvs: per receiver
+        ``(out row, index of its own row, w_self, [(source index, weight), ...])`` in fold
+        order.  Weights are Python floats, rounded to fp32 here as torch rounds a scalar."""
+        src_ptrs = _row_ptrs(srcs, srcs.shape[0] if isinstance(srcs, torch.Tensor) else len(srcs))
+        self.n_src, self.m = len(src_ptrs), len(recvs)
+        self.n_entries = sum(len(r[3]) for r in recvs)
+        self.reads = self.n_entries + self.m  # row reads of the direct path
+        words = np.zeros(max(1, self.n_src + 4 * self.m + self.n_entries), dtype=np.uint64)
+        words[:self.n_src] = src_ptrs
+        halves = words.view(np.uint32)  # little endian: [2 i] the low half of word i
+        ent = self.n_src + 4 * self.m
+        start = 0
+        for j, (out, own, w_self, pairs) in enumerate(recvs):
+            b = self.n_src + 4 * j
+            words[b] = out.data_ptr()
+            halves[2 * b + 2:2 * b + 6] = (np.int32(own).view(np.uint32),
+                                           np.float32(w_self).view(np.uint32), start, len(pairs))
+            for src, w in pairs:
+                halves[2 * (ent + start)] = np.int32(src).view(np.uint32)
+                halves[2 * (ent + start) + 1] = np.float32(w).view(np.uint32)
+                start += 1
+        self.host = words
+        self.dev = torch.from_numpy(words.view(np.int64)).to(device)
+
+
+def dense_average_nodes(table, n, mode=_lib.DPZ_DENSE_AUTO, check_rc=True):
+    """Every receiver's dense fold of ``table`` (a ``DenseTable``) in one launch: out = the
+    weighted sum of its list's source rows in list order plus ``w_self`` times its own row, in
+    the fp32 order of the dense ``decode_average``; an empty list copies the own row.  mode:
+    DPZ_DENSE_AUTO / _STAGED / _DIRECT.  Returns the library's code (raises unless it is DPZ_OK
+    when ``check_rc``)."""
+    _require(table.dev, torch.int64, "table")
+    rc = _lib.lib().dpz_dense_average_nodes(
+        table.m, _ptr(table.dev), ctypes.c_void_p(table.host.ctypes.data), table.n_entries,
+        table.n_src, int(n), int(mode), _stream(table.dev.device))
+    if check_rc:
+        check(rc, "dpz_dense_average_nodes")
+    return rc
 
 
 class QuantInfo:

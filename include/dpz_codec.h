@@ -792,6 +792,41 @@ int dpz_quant_encode(const float* x, int64_t n, int64_t k, uint8_t* body, int64_
 int dpz_quant_decode(const uint8_t* body, int64_t body_bytes, int64_t n, int w, double scale,
                      float* out, dpz_stream_t stream);
 
+/* ---- Dense folds of a round's nodes at once (decentralizepy_amd/gossip_epidemic.py) -----------
+ * Full-model rounds (Epidemic Learning's PlainAverageSharing, the D-PSGD full share of class
+ * Sharing): m receivers fold whole source rows in ONE launch.  fold_table is a DEVICE array of
+ * 64-bit words: n_src source row pointers (fp32 rows of n elements: the flat models of the
+ * round), then m receivers of 4 words {out, self (int32: the index of its own row) | w_self
+ * (fp32) in the high half, start (int32) | count (int32) in the high half, 0}, then n_entries
+ * list entries {src (int32) | w (fp32) in the high half}; receiver j folds the entries
+ * [start_j, start_j + count_j) in that order.  A list may have any length.  host_table is the
+ * HOST copy of the same words: every check below is made on it, before anything is enqueued.
+ * Each element is folded exactly as by the dense-payload DPZ_FOLD_SELF form of
+ * dpz_decode_average: t = fl(v_0 w_0), t = fl(t + fl(v_i w_i)) in list order,
+ * out = fl(t + fl(local w_self)); a receiver with an empty list gets a bitwise copy of its own
+ * row (the reference leaves such a node's model untouched, EL_Local.py:162-165).
+ * mode: DPZ_DENSE_STAGED stages a column tile of every source row in LDS once and forms every
+ * receiver's output from it (a tile of dpz_dense_tile_elems(n_src) elements: the largest of 1024 /
+ * 512 / 256 with n_src * tile * 4 bytes <= 64 KiB, 0 when none fits: DPZ_ERR_UNSUPPORTED);
+ * DPZ_DENSE_DIRECT runs a grid of tiles x receivers, each receiver streaming its sources from
+ * memory; DPZ_DENSE_AUTO takes the path dpz_dense_auto_mode(n_src, sum(count_j + 1), n) names:
+ * staged iff a tile fits, 2 n_src <= sum(count_j + 1) (staging at least halves the row reads) and
+ * n spans at least 384 tiles (measured: below that the staged grid, tiles only, leaves the machine
+ * idle and the direct path is faster).  Rows that are
+ * all 16-byte aligned take 16-byte loads and stores, otherwise every access is per element.
+ * DPZ_ERR_ARG: null pointers, m < 1, n < 1, n_src < 1, a mode outside 0 .. 2, an index outside
+ * [0, n_src), a list outside [0, n_entries), an out row that equals or overlaps a source row or
+ * another out row (receivers write while others still read: the caller double-buffers).
+ * DPZ_ERR_UNSUPPORTED: n >= 2^31 or m > 65535.                                                  */
+#define DPZ_DENSE_AUTO 0
+#define DPZ_DENSE_STAGED 1
+#define DPZ_DENSE_DIRECT 2
+int64_t dpz_dense_tile_elems(int n_src);
+int dpz_dense_auto_mode(int n_src, int64_t row_reads, int64_t n);
+int dpz_dense_average_nodes(int m, const void* fold_table, const void* host_table,
+                            int64_t n_entries, int n_src, int64_t n, int mode,
+                            dpz_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
