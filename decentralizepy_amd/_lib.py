@@ -238,6 +238,13 @@ SIGNATURES = {
     "dpz_dense_auto_mode": (_int, [_int, _i64, _i64]),
     "dpz_dense_average_nodes": (_int, [_int, _c_void_p, _c_void_p, _i64, _int, _i64, _int,
                                        _c_void_p]),
+    "dpz_choco_chunk_elems": (_i64, []),
+    "dpz_choco_tile_elems": (_i64, []),
+    "dpz_choco_encode_workspace_bytes": (_size, [_int, _i64]),
+    "dpz_choco_encode_nodes": (_int, [_int, _c_void_p, _i64, _i64, _i64, _c_void_p, _size,
+                                      _c_void_p]),
+    "dpz_choco_fold_nodes": (_int, [_int, _c_void_p, _c_void_p, _i64, _i64, ctypes.c_float,
+                                    _c_void_p, _i64, _c_void_p]),
 }
 
 _lib = None

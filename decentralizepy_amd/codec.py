@@ -28,7 +28,8 @@ __all__ = ["DPZ_ACC_NONE", "DPZ_ACC_ACCUMULATE", "DPZ_ACC_ADD", "DPZ_EW_SUB", "D
            "gather_node_table", "mask_gather_nodes", "fold_node_table",
            "mask_decode_average_nodes", "quant_encode", "quant_decode",
            "quant_block_elems", "QuantInfo", "dense_tile_elems", "dense_auto_mode", "DenseTable",
-           "dense_average_nodes"]
+           "dense_average_nodes", "choco_chunk_elems", "choco_tile_elems", "choco_node_table",
+           "choco_encode_nodes", "ChocoTable", "choco_fold_nodes"]
 
 
 def _ptr(t):
@@ -1439,6 +1440,92 @@ def dense_average_nodes(table, n, mode=_lib.DPZ_DENSE_AUTO, check_rc=True):
         table.n_src, int(n), int(mode), _stream(table.dev.device))
     if check_rc:
         check(rc, "dpz_dense_average_nodes")
+    return rc
+
+
+def choco_chunk_elems():
+    """Elements one block of ``choco_encode_nodes``' count and compaction passes covers."""
+    return int(_lib.lib().dpz_choco_chunk_elems())
+
+
+def choco_tile_elems():
+    """Elements of one receiver a block of ``choco_fold_nodes`` owns."""
+    return int(_lib.lib().dpz_choco_tile_elems())
+
+
+def choco_node_table(x, x_hat, rows):
+    """The DEVICE node table of ``choco_encode_nodes``: 4 64-bit words per node {x, x_hat, packed
+    row, 0}.  Each argument is a 2-D tensor (one row per node) or a list of per-node tensors."""
+    m = x.shape[0] if isinstance(x, torch.Tensor) else len(x)
+    dev = (x if isinstance(x, torch.Tensor) else x[0]).device
+    cols = [_row_ptrs(t, m) for t in (x, x_hat, rows)] + [[0] * m]
+    tab = np.array(cols, dtype=np.uint64).T.copy()
+    return torch.from_numpy(tab.view(np.int64)).to(dev)
+
+
+def choco_encode_nodes(table, n, k, cap, workspace=None):
+    """Choco's ``_pre_step`` + ``serialized_model`` of every node of ``table``
+    (``choco_node_table``): per node the threshold selection of ``topk_threshold(x - x_hat, k)``
+    into its packed row ``[count (int64), status, 0 | cap idx | cap vals]``, status 1 and nothing
+    written past ``cap`` when more are selected.  One launch set for all nodes, nothing read back.
+    ``workspace``: a uint8 device tensor kept by the caller (allocated here when None); returned."""
+    _require(table, torch.int64, "table")
+    m = table.shape[0]
+    need = int(_lib.lib().dpz_choco_encode_workspace_bytes(m, int(n)))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=table.device)
+    rc = _lib.lib().dpz_choco_encode_nodes(m, _ptr(table), int(n), int(k), int(cap),
+                                           _ptr(workspace), workspace.numel(),
+                                           _stream(table.device))
+    check(rc, "dpz_choco_encode_nodes")
+    return workspace
+
+
+class ChocoTable:
+    """The fold table of ``choco_fold_nodes``: the DEVICE words and the host copy the library
+    validates (kept alive here), with the counts the call repeats."""
+
+    def __init__(self, recvs, device):
+        """recvs: per receiver ``(x, x_hat, s, own packed row, own cap, w_self, [(packed row,
+        cap, weight), ...])``, the list in fold order.  Rows are tensors or device addresses;
+        weights are Python floats, rounded to fp32 here as torch rounds a scalar."""
+        def ptr(t):
+            return t.data_ptr() if isinstance(t, torch.Tensor) else int(t)
+
+        self.m = len(recvs)
+        self.n_entries = sum(len(r[6]) for r in recvs)
+        words = np.zeros(max(1, 6 * self.m + 2 * self.n_entries), dtype=np.uint64)
+        halves = words.view(np.uint32)  # little endian: [2 i] the low half of word i
+        ent, start = 6 * self.m, 0
+        for j, (x, x_hat, s, row, cap, w_self, pays) in enumerate(recvs):
+            b = 6 * j
+            words[b:b + 4] = (ptr(x), ptr(x_hat), ptr(s), ptr(row))
+            halves[2 * b + 8:2 * b + 12] = (np.float32(w_self).view(np.uint32),
+                                            np.int32(cap).view(np.uint32), start, len(pays))
+            for prow, pcap, w in pays:
+                e = ent + 2 * start
+                words[e] = ptr(prow)
+                halves[2 * e + 2] = np.float32(w).view(np.uint32)
+                halves[2 * e + 3] = np.int32(pcap).view(np.uint32)
+                start += 1
+        self.host = words
+        self.dev = torch.from_numpy(words.view(np.int64)).to(device)
+
+
+def choco_fold_nodes(table, n, step_size, guard=None, check_rc=True):
+    """Choco's ``_averaging`` of every receiver of ``table`` (a ``ChocoTable``) in one launch, in
+    place: ``x_hat += q_self``; ``s += w_p T_p`` in list order, ``+= w_self q_self``;
+    ``x += step_size (s - x_hat)``, each operation rounded to fp32 on its own.  ``guard`` (int32
+    device words, e.g. the rows' status words): nothing is written if any is nonzero.  Returns
+    the library's code (raises unless it is DPZ_OK when ``check_rc``)."""
+    _require(table.dev, torch.int64, "table")
+    _require(guard, torch.int32, "guard")
+    rc = _lib.lib().dpz_choco_fold_nodes(
+        table.m, _ptr(table.dev), ctypes.c_void_p(table.host.ctypes.data), table.n_entries,
+        int(n), float(step_size), _ptr(guard), guard.numel() if guard is not None else 0,
+        _stream(table.dev.device))
+    if check_rc:
+        check(rc, "dpz_choco_fold_nodes")
     return rc
 
 

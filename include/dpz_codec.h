@@ -827,6 +827,57 @@ int dpz_dense_average_nodes(int m, const void* fold_table, const void* host_tabl
                             int64_t n_entries, int n_src, int64_t n, int mode,
                             dpz_stream_t stream);
 
+/* ---- A Choco-SGD round of a rank's nodes at once (decentralizepy_amd/gossip_choco.py) ----------
+ * Reference sharing/Choco.py:186-207 (threshold sparsification), :359-453 (the round).  A node's
+ * packed row is [count (int64), status (int32), 0 | cap x int32 idx | cap x fp32 val], 4-byte
+ * aligned (the count is written and read as two 32-bit words; it is below 2^31).
+ * dpz_choco_encode_nodes: `_pre_step` + `serialized_model` of m nodes of one size n.  node_table
+ * is a DEVICE array of m entries of 4 64-bit words {x, x_hat, row, 0}.  Per node, exactly what
+ * dpz_topk_threshold selects from d = fl(x - x_hat), which is never written to memory: T = the
+ * k-th largest |d| (NaN ranks above +inf), every i with |d_i| >= T and d_i != 0 in ascending
+ * index order, all ties kept, no exact zeros when T == 0; idx = i, val = d_i.  The row's count is
+ * the number selected, status = (count > cap) ? 1 : 0, and nothing is written at or past idx + cap
+ * or val + cap: an overflow is reported, never silently truncated.  x and x_hat are read with
+ * 16-byte loads where both rows are 16-byte aligned, per element otherwise.  One memset and nine
+ * launches whatever m is (the node is the grid's second dimension): three histogram passes, each
+ * with a 1-block-per-node resolve, a count pass over chunks of dpz_choco_chunk_elems() elements,
+ * a 1-block-per-node scan and the ordered compaction; no host synchronisation, no copy to the
+ * host.  ws: dpz_choco_encode_workspace_bytes(m, n) DEVICE bytes, 4-byte aligned, any content.
+ * All checks come before anything is enqueued: DPZ_ERR_ARG for m < 1, n < 1, k < 1 (the k = 0
+ * "send everything" branch stays with the per-node plugin), k > n, cap < 1 or null pointers;
+ * DPZ_ERR_UNSUPPORTED for n >= 2^31 or m > 65535; DPZ_ERR_WORKSPACE for a short workspace.
+ * dpz_choco_fold_nodes: `_averaging` of m receivers in ONE launch, in place on each receiver's
+ * x, x_hat and s rows (fp32, n elements).  fold_table is a DEVICE array of 64-bit words: m
+ * receivers of 6 words {x, x_hat, s, its own packed row, w_self (fp32) | its row's cap (int32) in
+ * the high half, start (int32) | count (int32) in the high half}, then n_entries list entries of
+ * 2 words {packed row, w (fp32) | that row's cap (int32) in the high half}; receiver j folds the
+ * entries [start_j, start_j + count_j) in that order, any count including 0.  host_table is the
+ * HOST copy of the same words: every check is made on it, before anything is enqueued.  The
+ * rows' counts are read from their headers on the device (clamped to the row's cap).  Per element
+ * j, with t_p[j] / q_self[j] the payload's value at j or 0 where it has no entry, one fp32
+ * rounding per operation:
+ *   x_hat' = fl(x_hat + q_self[j]);  s' = s;  s' = fl(s' + fl(t_p[j] w_p)) in list order;
+ *   s' = fl(s' + fl(q_self[j] w_self));  x' = fl(x + fl(step_size fl(s' - x_hat')))
+ * which is, bit for bit, dpz_elementwise(DPZ_EW_ADD), dpz_decode_average(DPZ_FOLD_ZERO_BASE |
+ * DPZ_FOLD_ACCUMULATE | DPZ_FOLD_SELF) and dpz_elementwise(DPZ_EW_CHOCO) as long as s and x_hat
+ * hold no -0 (they never do when they start at +0: dpz_choco.hip), a payload's indices are
+ * ascending and unique and the weights are finite.  A block owns a tile of
+ * dpz_choco_tile_elems() elements of one receiver; there is no n-length temporary.  The launch
+ * first reads guard[0, guard_n) (DEVICE int32, may be NULL with guard_n = 0, e.g. the gathered
+ * rows' status words) and writes nothing at all if any word is nonzero.
+ * DPZ_ERR_ARG: null pointers, m < 1, n < 1, a list outside [0, n_entries), a cap < 1, a
+ * non-finite weight or step_size, a misaligned pointer, guard_n < 0 or guard words without a
+ * guard, an x / x_hat / s row that overlaps any other row of the table (payload rows included:
+ * receivers write while others read).  DPZ_ERR_UNSUPPORTED: n >= 2^31 or m > 65535.            */
+int64_t dpz_choco_chunk_elems(void);
+int64_t dpz_choco_tile_elems(void);
+size_t dpz_choco_encode_workspace_bytes(int m, int64_t n);
+int dpz_choco_encode_nodes(int m, const void* node_table, int64_t n, int64_t k, int64_t cap,
+                           void* ws, size_t ws_bytes, dpz_stream_t stream);
+int dpz_choco_fold_nodes(int m, const void* fold_table, const void* host_table, int64_t n_entries,
+                         int64_t n, float step_size, const int32_t* guard, int64_t guard_n,
+                         dpz_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
