@@ -190,13 +190,30 @@ constexpr int DWT_SPAN0 = 16 * DWT_TL + 64;  // level-0 span (covers L <= 4 with
 constexpr int DWT_SPAN1 = 8 * DWT_TL + 32;
 constexpr int DWT_NG = (DWT_SPAN0 + 4 + 4 * 256 - 1) / (4 * 256);  // float4 groups per thread
 
-// level-0 input span [s0, e0) of a tile (its level-L outputs [a, b) and the halos below)
+// First level-L output a span-path tile COMPUTES (it owns [tile * TL, ...)).  A last tile that
+// owns a single output a = len[L] - 1 of an odd-length level-(L-1) input (len[L-1] = 2a - 1)
+// takes pywt's odd-tail order, which reads x~[n+1], x~[n+2] = the level-(L-1) values n-2, n-3 =
+// 2a-3, 2a-4: left of the span 2a-2 the owned output alone asks for, so the extension fix-up
+// found no source in LDS and the tail read unwritten slots (the last cA_L and the last cD_L —
+// all such a tile owns — were wrong at 2^(L-1) of every 2^L * TL lengths).  Such a tile starts
+// one output earlier at level L — every level below then reaches len[l-1] - 3 — and stores only
+// what it owns.  Its level-0 span starts 3 * 2^L - 2 inputs before 2^L * a instead of 2 (2^L - 1).
+__device__ __forceinline__ int64_t dwt_tile_first(const Levels& LV, int64_t tile) {
+  const int L = LV.level;
+  const int64_t a = tile * DWT_TL;
+  return (a > 0 && a + 1 == LV.len[L] && (LV.len[L - 1] & 1)) ? a - 1 : a;
+}
+
+// level-0 input span [s0, e0) of a tile (its level-L outputs [a, b) and the halos below); EDGE:
+// a span-path tile (dwt_tile_first), never needed by an interior tile
+template <bool EDGE = true>
 __device__ __forceinline__ void dwt_span(const Levels& LV, int64_t tile, int64_t* s0,
                                          int64_t* e0) {
   const int L = LV.level;
   const int64_t nL = LV.len[L];
   int64_t sl = tile * DWT_TL;
   int64_t el = (sl + DWT_TL < nL) ? sl + DWT_TL : nL;
+  if (EDGE) sl = dwt_tile_first(LV, tile);
   for (int l = L; l >= 1; --l) {
     sl = 2 * sl - 2;
     el = 2 * el;
@@ -289,7 +306,7 @@ __device__ __forceinline__ void dwt_levels(const Levels& LV, float* cx, float* c
   const bool last_block = (b == nL);
   // needed ranges per level (top-down)
   int64_t s[DWT_MAX_LEVEL + 1], e[DWT_MAX_LEVEL + 1];
-  s[L] = a;
+  s[L] = dwt_tile_first(LV, tile);  // a, or a - 1 (computed, not owned) for a one-output tail
   e[L] = b;
   for (int l = L; l >= 1; --l) {
     s[l - 1] = 2 * s[l] - 2;
@@ -630,7 +647,7 @@ __global__ void __launch_bounds__(256, (ACCUM && WD && DPZ_DWT_ACC_PRE) ? DPZ_DW
   float4 va[DWT_NG], vb[DWT_NG];
   float2 hx[DWT_NG], hb[DWT_NG];
   int64_t s0, e0;
-  dwt_span(LV, tile, &s0, &e0);
+  dwt_span<false>(LV, tile, &s0, &e0);
   dwt_span_load<WD>(x, x0, n, s0, e0, va, vb);
   dwt_halo_load<WD>(x, x0, s0 & ~int64_t(3), hx, hb);
   constexpr bool PRE = ACCUM && WD && DPZ_DWT_ACC_PRE != 0;
@@ -641,7 +658,7 @@ __global__ void __launch_bounds__(256, (ACCUM && WD && DPZ_DWT_ACC_PRE) ? DPZ_DW
     // the next tile's loads are in flight while this tile's levels 2-4 are computed
     const int64_t next = tile + gridDim.x;
     if (next < b) {
-      dwt_span(LV, next, &s0, &e0);
+      dwt_span<false>(LV, next, &s0, &e0);
       dwt_span_load<WD>(x, x0, n, s0, e0, va, vb);
       dwt_halo_load<WD>(x, x0, s0 & ~int64_t(3), hx, hb);
     }

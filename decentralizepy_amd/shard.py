@@ -216,7 +216,9 @@ def tile_widths():
 def halo_len(level):
     """Left halo a forward slice needs: 2 (2^L - 1) inputs, rounded up to 4 so that the halo'd
     buffer keeps the kernel's float4 groups (which start at a multiple of 4) aligned and inside
-    the buffer."""
+    the buffer.  (The one-output tail tile that reads 3 * 2^L - 2 inputs back, dpz_codec.h, is
+    never a rank's first tile: n < 2^L * W * t there, so wavelet_slice starts the rank's slice,
+    a multiple of the inverse tile below n, at least one forward tile earlier.)"""
     return (2 * ((1 << level) - 1) + 3) // 4 * 4
 
 

@@ -464,8 +464,11 @@ int dpz_idwt_sym2(const float* coeffs, int64_t n, int level, float* out, dpz_str
  * DWT/IDWT: yes, with a halo"; decentralizepy_amd/shard.py sharded_wavedec / sharded_waverec).
  * The forward tile t owns level-L outputs [t*W, (t+1)*W) (W = dpz_dwt_tile_width()) and the
  * matching 2^(L-l)*W outputs of every detail level; it reads inputs [2^L*W*t - 2(2^L - 1),
- * 2^L*W*(t+1)) of x / x0 (clipped to [0, n)).  The inverse tile u writes outputs
- * [u*V, (u+1)*V) (V = dpz_idwt_tile_width()).  x, x0, coeffs and out are VIRTUAL bases: element i
+ * 2^L*W*(t+1)) of x / x0 (clipped to [0, n)); a last tile that owns a single level-L output of
+ * an odd-length level-(L-1) input reads from 2^L*W*t - (3*2^L - 2): all of it lies left of
+ * 2^L*W*t (n is smaller), in the slice of the rank that holds the array's tail.  The inverse
+ * tile u writes outputs [u*V, (u+1)*V) (V = dpz_idwt_tile_width()).  x, x0, coeffs and out are
+ * VIRTUAL bases: element i
  * of the global array is at base + i, and only the elements the tiles [tile_lo, tile_hi) touch
  * are dereferenced (a rank passes its halo'd slice buffer minus its first global index).        */
 int64_t dpz_dwt_tile_width(void);
