@@ -1326,17 +1326,29 @@ def _row_ptrs(rows, m):
     return [t.data_ptr() for t in rows]
 
 
+def _f32_bits(v):
+    """The fp32 bits of a Python number, rounded as torch rounds a scalar."""
+    return int(np.float32(v).view(np.uint32))
+
+
+def _i32_bits(v):
+    return int(np.int32(v).view(np.uint32))
+
+
+def _ptr_table(cols, m, device):
+    """A DEVICE node table: ``cols`` (tensors with a row per node, lists of per-node tensors, or
+    None for a zero column) as the row pointers of an (m, len(cols)) int64 table."""
+    tab = np.array([_row_ptrs(c, m) for c in cols], dtype=np.uint64).T.copy()
+    return torch.from_numpy(tab.view(np.int64)).to(device)
+
+
 def gather_node_table(x, mask, rank_tab, vals, count, status, counter=None):
     """The DEVICE node table of ``mask_gather_nodes``: 8 64-bit words per node {x, mask, rank_tab,
     vals, counter or 0, count, status, 0}.  Every argument is a 2-D tensor (one row per node) or
     a list of per-node tensors; ``count`` (int64) and ``status`` (int32) are 1-D (any stride), one
     word per node."""
-    m = x.shape[0] if isinstance(x, torch.Tensor) else len(x)
     dev = (x if isinstance(x, torch.Tensor) else x[0]).device
-    cols = [_row_ptrs(t, m) for t in (x, mask, rank_tab, vals, counter)]
-    cols += [_row_ptrs(count, m), _row_ptrs(status, m), [0] * m]
-    tab = np.array(cols, dtype=np.uint64).T.copy()
-    return torch.from_numpy(tab.view(np.int64)).to(dev)
+    return _ptr_table((x, mask, rank_tab, vals, counter, count, status, None), len(x), dev)
 
 
 def mask_gather_nodes(table, n, cap):
@@ -1354,19 +1366,16 @@ def fold_node_table(dests, device):
     counts.  ``dests``: per destination ``(local, out, w_self or None, [(mask, rank_tab, vals,
     w), ...])`` with 1..16 payloads; 68 64-bit words each: {local, out, w_self, n_payloads}, then
     {mask, rank_tab, vals, w} per payload (weights as fp32 bits in the low half of their word)."""
-    def f32(v):
-        return int(np.float32(v).view(np.uint32))
-
     tab = np.zeros((max(1, len(dests)), 4 + 4 * MASK_FOLD_MAX), dtype=np.uint64)
     counts = (ctypes.c_int * max(1, len(dests)))()
     for j, (local, out, w_self, pays) in enumerate(dests):
         counts[j] = len(pays)
-        tab[j, :4] = (local.data_ptr(), out.data_ptr(), f32(w_self or 0.0), len(pays))
+        tab[j, :4] = (local.data_ptr(), out.data_ptr(), _f32_bits(w_self or 0.0), len(pays))
         for p, (mask, rank_tab, vals, w) in enumerate(pays[:MASK_FOLD_MAX]):
             if vals.numel() == 0:  # an empty selection: never read, but kept a valid address
                 vals = local
             tab[j, 4 + 4 * p:8 + 4 * p] = (mask.data_ptr(), rank_tab.data_ptr(), vals.data_ptr(),
-                                           f32(w))
+                                           _f32_bits(w))
     return torch.from_numpy(tab.view(np.int64)).to(device), counts
 
 
@@ -1398,9 +1407,21 @@ def dense_auto_mode(n_src, row_reads, n):
     return int(_lib.lib().dpz_dense_auto_mode(int(n_src), int(row_reads), int(n)))
 
 
-class DenseTable:
-    """The fold table of ``dense_average_nodes``: the DEVICE words and the host copy the library
-    validates (kept alive here), with the counts the call repeats."""
+class _WordTable:
+    """A fold table of 64-bit words: ``host``, the copy the library validates (kept alive here),
+    and ``dev``, the DEVICE words."""
+
+    def _words(self, n_words):
+        self.host = np.zeros(max(1, n_words), dtype=np.uint64)
+        return self.host, self.host.view(np.uint32)  # little endian: [2 i] the low half of word i
+
+    def _upload(self, device):
+        self.dev = torch.from_numpy(self.host.view(np.int64)).to(device)
+
+
+class DenseTable(_WordTable):
+    """The fold table of ``dense_average_nodes`` (a ``_WordTable``), with the counts the call
+    repeats."""
 
     def __init__(self, srcs, recvs, device):
         """srcs: the source rows (a 2-D tensor or a list of 1-D tensors); recvs: per receiver
@@ -1410,22 +1431,18 @@ class DenseTable:
         self.n_src, self.m = len(src_ptrs), len(recvs)
         self.n_entries = sum(len(r[3]) for r in recvs)
         self.reads = self.n_entries + self.m  # row reads of the direct path
-        words = np.zeros(max(1, self.n_src + 4 * self.m + self.n_entries), dtype=np.uint64)
+        words, halves = self._words(self.n_src + 4 * self.m + self.n_entries)
         words[:self.n_src] = src_ptrs
-        halves = words.view(np.uint32)  # little endian: [2 i] the low half of word i
         ent = self.n_src + 4 * self.m
         start = 0
         for j, (out, own, w_self, pairs) in enumerate(recvs):
             b = self.n_src + 4 * j
             words[b] = out.data_ptr()
-            halves[2 * b + 2:2 * b + 6] = (np.int32(own).view(np.uint32),
-                                           np.float32(w_self).view(np.uint32), start, len(pairs))
+            halves[2 * b + 2:2 * b + 6] = (_i32_bits(own), _f32_bits(w_self), start, len(pairs))
             for src, w in pairs:
-                halves[2 * (ent + start)] = np.int32(src).view(np.uint32)
-                halves[2 * (ent + start) + 1] = np.float32(w).view(np.uint32)
+                halves[2 * (ent + start):2 * (ent + start) + 2] = (_i32_bits(src), _f32_bits(w))
                 start += 1
-        self.host = words
-        self.dev = torch.from_numpy(words.view(np.int64)).to(device)
+        self._upload(device)
 
 
 def dense_average_nodes(table, n, mode=_lib.DPZ_DENSE_AUTO, check_rc=True):
@@ -1456,11 +1473,8 @@ def choco_tile_elems():
 def choco_node_table(x, x_hat, rows):
     """The DEVICE node table of ``choco_encode_nodes``: 4 64-bit words per node {x, x_hat, packed
     row, 0}.  Each argument is a 2-D tensor (one row per node) or a list of per-node tensors."""
-    m = x.shape[0] if isinstance(x, torch.Tensor) else len(x)
     dev = (x if isinstance(x, torch.Tensor) else x[0]).device
-    cols = [_row_ptrs(t, m) for t in (x, x_hat, rows)] + [[0] * m]
-    tab = np.array(cols, dtype=np.uint64).T.copy()
-    return torch.from_numpy(tab.view(np.int64)).to(dev)
+    return _ptr_table((x, x_hat, rows, None), len(x), dev)
 
 
 def choco_encode_nodes(table, n, k, cap, workspace=None):
@@ -1481,9 +1495,9 @@ def choco_encode_nodes(table, n, k, cap, workspace=None):
     return workspace
 
 
-class ChocoTable:
-    """The fold table of ``choco_fold_nodes``: the DEVICE words and the host copy the library
-    validates (kept alive here), with the counts the call repeats."""
+class ChocoTable(_WordTable):
+    """The fold table of ``choco_fold_nodes`` (a ``_WordTable``), with the counts the call
+    repeats."""
 
     def __init__(self, recvs, device):
         """recvs: per receiver ``(x, x_hat, s, own packed row, own cap, w_self, [(packed row,
@@ -1494,22 +1508,18 @@ class ChocoTable:
 
         self.m = len(recvs)
         self.n_entries = sum(len(r[6]) for r in recvs)
-        words = np.zeros(max(1, 6 * self.m + 2 * self.n_entries), dtype=np.uint64)
-        halves = words.view(np.uint32)  # little endian: [2 i] the low half of word i
+        words, halves = self._words(6 * self.m + 2 * self.n_entries)
         ent, start = 6 * self.m, 0
         for j, (x, x_hat, s, row, cap, w_self, pays) in enumerate(recvs):
             b = 6 * j
             words[b:b + 4] = (ptr(x), ptr(x_hat), ptr(s), ptr(row))
-            halves[2 * b + 8:2 * b + 12] = (np.float32(w_self).view(np.uint32),
-                                            np.int32(cap).view(np.uint32), start, len(pays))
+            halves[2 * b + 8:2 * b + 12] = (_f32_bits(w_self), _i32_bits(cap), start, len(pays))
             for prow, pcap, w in pays:
                 e = ent + 2 * start
                 words[e] = ptr(prow)
-                halves[2 * e + 2] = np.float32(w).view(np.uint32)
-                halves[2 * e + 3] = np.int32(pcap).view(np.uint32)
+                halves[2 * e + 2:2 * e + 4] = (_f32_bits(w), _i32_bits(pcap))
                 start += 1
-        self.host = words
-        self.dev = torch.from_numpy(words.view(np.int64)).to(device)
+        self._upload(device)
 
 
 def choco_fold_nodes(table, n, step_size, guard=None, check_rc=True):

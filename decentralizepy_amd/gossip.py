@@ -34,9 +34,10 @@ The encode / fold callables are injectable so the sharding and exchange logic ca
 the CPU gloo backend; the defaults are the HIP codec (no CPU fallback).
 """
 import ctypes
-import math
 
 import torch
+
+from .gossip_round import ShardedRound, shard  # noqa: F401 - shard is part of this module's surface
 
 
 def read_edges(path):
@@ -71,15 +72,7 @@ def mh_weights(adj, i):
     return nbrs, w, 1 - total
 
 
-def shard(n_nodes, world, rank):
-    """Contiguous node block of `rank` and the padded per-rank count for the all-gather."""
-    per = math.ceil(n_nodes / world)
-    lo = min(rank * per, n_nodes)
-    hi = min(lo + per, n_nodes)
-    return lo, hi, per
-
-
-class GossipRound:
+class GossipRound(ShardedRound):
     """Nodes [lo, hi) of a topology on this rank; ``step()`` runs one full round."""
 
     def __init__(self, adj, x_init, alpha, rank=0, world=1, group=None, encode=None, fold=None,
@@ -95,7 +88,7 @@ class GossipRound:
         reduce-scatter; default budget: half of the device's free memory at construction).  ``partial(payloads, weights, out)``
         (zero-based weighted sum of sparse payloads) and ``combine(x, B, A, c, out)`` are
         injectable like encode / fold (CPU tests); the defaults are the HIP codec."""
-        self.adj = adj
+        super().__init__(adj, x_init, rank, world, group, device)
         # node_batch: the HIP encodes of this rank's nodes in groups of `node_group` nodes, one
         # launch per phase and group (dpz_topk_encode_nodes), the groups round-robin over
         # `streams`; False: node after node on the streams.  Measured on MI355X (96_regular x
@@ -107,17 +100,7 @@ class GossipRound:
         # guarded: (HIP, all-gather exchange) the folds follow the encodes with no host wait in
         # between, guarded on the device by the encodes' status words (_step_guarded)
         self.guarded = guarded
-        self.n_nodes = len(adj)
-        self.rank, self.world, self.group = rank, world, group
-        # the exchange runs through the collectives with more than one rank, or whenever the
-        # caller hands over a process group (one rank too: the RCCL path then runs as a loopback,
-        # tests/test_gpu_rccl.py); one rank without a group exchanges in place
-        self.coll = world > 1 or group is not None
-        self.lo, self.hi, self.per = shard(self.n_nodes, world, rank)
-        assert x_init.shape[0] == self.hi - self.lo
-        self.N = x_init.shape[1]
         self.k = round(alpha * self.N)
-        self.device = device or x_init.device
         self.x = x_init.contiguous().clone()
         self.x0 = x_init.contiguous().clone()  # init_model of every owned node
         # sliced_counter (HIP, node-batched encodes): every node's shared_parameters_counter as 32

@@ -20,23 +20,20 @@ needs a larger ``slot_cap``.  An overflow is reported by ``check()``, never trun
 The encode / fold callables are injectable together so the sharding and exchange logic can be
 tested with the CPU gloo backend; the defaults are the HIP codec (no CPU fallback).
 """
-import numpy as np
 import torch
 
-from .gossip import mh_weights, shard
-from .gossip_subsampling import HEADER
+from .gossip import mh_weights
+from .gossip_round import PackedRowRound, up4
 
-
-def _up4(v):
-    return -(-int(v) // 4) * 4
+HEADER = PackedRowRound.HEADER
 
 
 def slot_capacity(n, k):
     """Entries a node's slot holds by default: ``min(n, k + max(64, k // 8))`` rounded up to 4."""
-    return _up4(min(int(n), int(k) + max(64, int(k) // 8)))
+    return up4(min(int(n), int(k) + max(64, int(k) // 8)))
 
 
-class ChocoRound:
+class ChocoRound(PackedRowRound):
     """Nodes [lo, hi) of a topology on this rank; ``step()`` runs one Choco round of every node.
     ``x`` is a writable view of the owned nodes' models: the caller applies its local training to
     it between rounds."""
@@ -53,13 +50,8 @@ class ChocoRound:
                              "implemented")
         if (encode is None) != (fold is None):
             raise ValueError("encode and fold are injected together")
-        self.adj, self.n_nodes = adj, len(adj)
-        self.rank, self.world, self.group = rank, world, group
-        self.coll = world > 1 or group is not None  # as GossipRound.coll
-        self.lo, self.hi, self.per = shard(self.n_nodes, world, rank)
-        m = self.hi - self.lo
-        assert x_init.shape[0] == m
-        self.N = N = x_init.shape[1]
+        super().__init__(adj, x_init, rank, world, group, device)
+        m, N = self.m, self.N
         self.alpha, self.step_size = float(alpha), float(step_size)
         self.k = round(self.alpha * N)
         if self.k < 1:
@@ -67,35 +59,22 @@ class ChocoRound:
                              "sparsification) stays with the per-node plugin")
         if self.k > N:
             raise ValueError("alpha must lie in (0, 1]")
-        self.device = device or x_init.device
         self._hip = encode is None
         self._encode, self._fold = encode, fold
-        self.cap = _up4(slot_cap) if slot_cap is not None else slot_capacity(N, self.k)
+        self.cap = up4(slot_cap) if slot_cap is not None else slot_capacity(N, self.k)
         f32 = dict(dtype=torch.float32, device=self.device)
-        i32 = dict(dtype=torch.int32, device=self.device)
-        stride = _up4(N)  # every row 16-byte aligned
+        stride = up4(N)  # every row 16-byte aligned
         self._state = torch.zeros(3, max(1, m), stride, **f32)
         self.x = self._state[0, :m, :N]
         self.x_hat = self._state[1, :m, :N]
         self.s = self._state[2, :m, :N]
         self.x.copy_(x_init)
         # a node's packed row: [count (int64), status, 0 | cap idx | cap vals]
-        self.row_words = W = HEADER + 2 * self.cap
-        self.send = torch.zeros(self.per, W, **i32)
-        self.recv = torch.zeros(self.per * world, W, **i32) if self.coll else None
-        self.guard = torch.zeros(self.per * world, **i32)
-        cuda = self.device.type == "cuda"
-        self._guard_host = torch.zeros(self.per * world, dtype=torch.int32, pin_memory=cuda)
+        self._alloc_rows(HEADER + 2 * self.cap)
         self.weights = [mh_weights(adj, i) for i in range(self.lo, self.hi)]
         self._enc_tab = self._fold_tab = self._ws = None
-        self.round = 0
 
     # ---- views of the packed rows ---------------------------------------------------------------
-    def _row(self, q):
-        """Node q's row as the folds read it: any node after an all-gather, an owned one
-        otherwise."""
-        return self.recv[q] if self.coll else self.send[q - self.lo]
-
     def _slots(self, row):
         return (row[HEADER:HEADER + self.cap],
                 row[HEADER + self.cap:HEADER + 2 * self.cap].view(torch.float32))
@@ -103,15 +82,17 @@ class ChocoRound:
     def payload(self, q):
         """``(idx, vals)`` of node q's payload of the last encode (an owned node; any node after
         an all-gather).  Reads the count: blocks."""
-        row = self._row(q)
-        count = min(int(row[:2].view(torch.int64).item()), self.cap)
+        return self._pay(self._row(q))
+
+    def _pay(self, row):
+        count = min(self._count_of(row), self.cap)
         idx, vals = self._slots(row)
         return idx[:count], vals[:count]
 
     # ---- the legs of a round --------------------------------------------------------------------
     def encode(self):
         """Every owned node's sparsified ``x - x_hat`` into its slot, with the row's header."""
-        m = self.hi - self.lo
+        m = self.m
         if not m:
             return
         if self._hip:
@@ -130,15 +111,6 @@ class ChocoRound:
             self.send[j, :2] = torch.tensor([idx.numel()], dtype=torch.int64).view(torch.int32)
             self.send[j, 2] = int(idx.numel() > self.cap)
 
-    def exchange(self):
-        """ONE all-gather of the packed rows; then the status words of every row, contiguous."""
-        if self.coll:
-            import torch.distributed as dist
-            dist.all_gather_into_tensor(self.recv, self.send, group=self.group)
-            self.guard.copy_(self.recv[:, 2])
-        else:
-            self.guard[:self.per].copy_(self.send[:, 2])
-
     def _recvs(self):
         """Per owned node: (x, x_hat, s, own row, cap, w_self, [(row, cap, w)]) in fold order."""
         out = []
@@ -150,7 +122,7 @@ class ChocoRound:
 
     def fold(self):
         """Every owned node's ``_averaging`` in place, behind the status words."""
-        m = self.hi - self.lo
+        m = self.m
         if not m:
             return
         if self._hip:
@@ -161,13 +133,9 @@ class ChocoRound:
             return
         if bool(self.guard.any()):
             return
-        for x, x_hat, s, own, _, w_self, pays in self._recvs():
-            def pay(row):
-                count = int(row[:2].view(torch.int64).item())
-                idx, vals = self._slots(row)
-                return idx[:count], vals[:count]
-            self._fold(x, x_hat, s, pay(own), w_self, [pay(r) + (w,) for r, _, w in pays],
-                       self.step_size)
+        for x, x_hat, s, own, _, w_self, pays in self._recvs():  # no status word: counts <= cap
+            self._fold(x, x_hat, s, self._pay(own), w_self,
+                       [self._pay(r) + (w,) for r, _, w in pays], self.step_size)
 
     def step(self, mark=None):
         """One round: the encode launch set, one all-gather (with a process group), one fold
@@ -188,14 +156,11 @@ class ChocoRound:
         RuntimeError naming the nodes whose selection exceeded the slot.  That round folded
         nothing: x, x_hat and s are those of before it, so the caller can rebuild the engine from
         them with a larger ``slot_cap``."""
-        cuda = self.device.type == "cuda"
-        self._guard_host.copy_(self.guard, non_blocking=cuda)
-        if cuda:
+        self._guard_to_host()
+        if self.device.type == "cuda":
             torch.cuda.current_stream(self.device).synchronize()
-        n = self.n_nodes if self.coll else self.per
-        bad = np.flatnonzero(self._guard_host.numpy()[:n])
-        if len(bad):
-            nodes = [int(b) + (0 if self.coll else self.lo) for b in bad]
+        nodes = self._bad_nodes()
+        if nodes:
             raise RuntimeError(
                 f"Choco round {self.round - 1}: nodes {nodes} select more than the slot's "
                 f"{self.cap} entries (ties at the threshold); nothing was folded")

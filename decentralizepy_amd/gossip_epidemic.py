@@ -24,14 +24,11 @@ from random import Random
 
 import torch
 
-from .gossip import mh_weights, shard
+from .gossip import mh_weights
+from .gossip_round import ShardedRound, up4
 
 
-def _up4(v):
-    return -(-int(v) // 4) * 4
-
-
-class DenseRound:
+class DenseRound(ShardedRound):
     """Nodes [lo, hi) of a topology on this rank; ``step()`` runs one round of every owned node.
     A subclass says who folds what: ``lists(t)`` returns, per owned node, ``(senders, weights,
     w_self)`` in fold order."""
@@ -47,15 +44,9 @@ class DenseRound:
             raise ValueError(f"unknown arguments {sorted(unknown)}: the peer exchange, the "
                              "over-HBM (reduce-scatter) exchange and compressed wire payloads "
                              "are not implemented for full-model rounds")
-        self.adj, self.n_nodes = adj, len(adj)
-        self.rank, self.world, self.group = rank, world, group
-        self.coll = world > 1 or group is not None  # as GossipRound.coll
-        self.lo, self.hi, self.per = shard(self.n_nodes, world, rank)
-        m = self.hi - self.lo
-        assert x_init.shape[0] == m
-        self.N = N = x_init.shape[1]
-        self.stride = S = _up4(N)
-        self.device = device or x_init.device
+        super().__init__(adj, x_init, rank, world, group, device)
+        m, N = self.m, self.N
+        self.stride = S = up4(N)
         self.mode = int(mode)
         self._fold = fold
         f32 = dict(dtype=torch.float32, device=self.device)
@@ -64,29 +55,23 @@ class DenseRound:
         self._cur[:m, :N].copy_(x_init)
         self.recv = torch.zeros(self.per * world, S, **f32) if self.coll else None
         self._tabs = {}
-        self.round = 0
 
     @property
     def x(self):
         """The owned nodes' models, (hi - lo, N)."""
-        return self._cur[:self.hi - self.lo, :self.N]
+        return self._cur[:self.m, :self.N]
 
     def lists(self, t):
         raise NotImplementedError
 
     # ---- the legs of a round --------------------------------------------------------------------
-    def _row_of(self, q):
-        """Node q's index among the fold's source rows."""
-        return q if self.coll else q - self.lo
-
     def _table(self, lists):
         from . import codec
         key = (self._cur.data_ptr(), self._nxt.data_ptr())
         if self.static and key in self._tabs:
             return self._tabs[key]
-        srcs = self.recv if self.coll else self._cur
-        recvs = [(self._nxt[j], self._row_of(self.lo + j), w_self,
-                  [(self._row_of(q), w) for q, w in zip(senders, weights)])
+        srcs = self.recv if self.coll else self._cur  # a node's number is its row in either
+        recvs = [(self._nxt[j], self.lo + j, w_self, list(zip(senders, weights)))
                  for j, (senders, weights, w_self) in enumerate(lists)]
         tab = codec.DenseTable(srcs, recvs, self.device)
         if self.static:
@@ -96,12 +81,10 @@ class DenseRound:
     def exchange(self):
         """ONE all-gather of the rank's rows (padded to ``per`` rows of ``stride`` floats)."""
         if self.coll:
-            import torch.distributed as dist
-            dist.all_gather_into_tensor(self.recv, self._cur, group=self.group)
+            self.all_gather(self.recv, self._cur)
 
     def fold(self, lists, table=None):
-        m = self.hi - self.lo
-        if not m:
+        if not self.m:
             return
         if self._fold is None:
             from . import codec
@@ -113,7 +96,7 @@ class DenseRound:
             if not senders:
                 out.copy_(self._cur[j, :self.N])
                 continue
-            self._fold(self._cur[j, :self.N], [src[self._row_of(q), :self.N] for q in senders],
+            self._fold(self._cur[j, :self.N], [src[q, :self.N] for q in senders],
                        weights, w_self, out)
 
     def step(self, mark=None):
@@ -122,7 +105,7 @@ class DenseRound:
         enqueued (tools/bench_epidemic_round.py records an event)."""
         mark = mark or (lambda leg: None)
         lists = self.lists(self.round)
-        table = self._table(lists) if self._fold is None and self.hi > self.lo else None
+        table = self._table(lists) if self._fold is None and self.m else None
         self.exchange()
         mark("exchange")
         self.fold(lists, table)

@@ -28,7 +28,8 @@ import random
 
 import torch
 
-from .gossip import mh_weights, shard
+from .gossip import mh_weights
+from .gossip_round import ShardedRound, shard
 
 ALIGN = 64  # payload slots start on 256-byte boundaries (the fold's 16-byte index loads)
 
@@ -154,7 +155,7 @@ class HipJwinsOps:
                            accumulate=True, wavelet=self.wavelet)
 
 
-class JwinsRound:
+class JwinsRound(ShardedRound):
     """Nodes [lo, hi) of a topology on this rank; ``step()`` runs one JWINS round of every node.
 
     Node i is uid i (the reference's Linear mapping of one process per node).  Per-node state,
@@ -166,13 +167,7 @@ class JwinsRound:
     def __init__(self, adj, x_init, alpha_list="[0.1, 0.2, 0.3, 0.4, 1.0]", rank=0, world=1,
                  group=None, wavelet="sym2", level=4, metadata_cap=0.5, ops=None, device=None,
                  m_len=None):
-        self.adj, self.n_nodes = adj, len(adj)
-        self.rank, self.world, self.group = rank, world, group
-        self.coll = world > 1 or group is not None  # as GossipRound.coll
-        self.lo, self.hi, self.per = shard(self.n_nodes, world, rank)
-        assert x_init.shape[0] == self.hi - self.lo
-        self.N = x_init.shape[1]
-        self.device = device or x_init.device
+        super().__init__(adj, x_init, rank, world, group, device)
         self.alpha_list = eval(alpha_list) if isinstance(alpha_list, str) else list(alpha_list)
         self.metadata_cap = metadata_cap
         if m_len is None:
@@ -225,7 +220,6 @@ class JwinsRound:
         if hasattr(self.ops, "reserve"):
             self.ops.reserve(M, sorted({round(a * M) for a in partial}))
         self.alphas = None
-        self.round = 0
 
     @property
     def counter(self):

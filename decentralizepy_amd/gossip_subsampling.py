@@ -20,12 +20,12 @@ the CPU gloo backend; the defaults are the HIP codec (no CPU fallback).
 """
 import math
 
-import numpy as np
 import torch
 
-from .gossip import mh_weights, shard
+from .gossip import mh_weights
+from .gossip_round import PackedRowRound, up4
 
-HEADER = 4  # int32 words in front of a row's values: the int64 count, the status word, 0
+HEADER = PackedRowRound.HEADER
 
 
 def slot_capacity(n, alpha):
@@ -35,14 +35,10 @@ def slot_capacity(n, alpha):
     mask.  A mask that does exceed the slot is reported by the round, never truncated silently."""
     a = float(alpha)
     cap = min(int(n), math.ceil(a * n + 8.0 * math.sqrt(max(0.0, a * n * (1.0 - a)))))
-    return -(-max(cap, 1) // 4) * 4
+    return up4(max(cap, 1))
 
 
-def _up4(v):
-    return -(-int(v) // 4) * 4
-
-
-class SubSamplingRound:
+class SubSamplingRound(PackedRowRound):
     """Nodes [lo, hi) of a topology on this rank; ``step()`` runs one SubSampling round of every
     node.  Node i is uid i; ``seeds[i]`` is its plugin's ``self.seed`` (the reference draws it from
     the random device; given here so that a run is reproducible), the mask of round t comes from
@@ -60,54 +56,34 @@ class SubSamplingRound:
                              "exchanges, full shares and payload compression are not implemented")
         if (encode is None) != (fold is None):
             raise ValueError("encode and fold are injected together")
-        self.adj, self.n_nodes = adj, len(adj)
-        if len(seeds) != self.n_nodes:
+        if len(seeds) != len(adj):
             raise ValueError("seeds must hold one integer per node of the topology")
         if not 0.0 < float(alpha) <= 1.0:
             raise ValueError("alpha must lie in (0, 1]")
-        self.rank, self.world, self.group = rank, world, group
-        self.coll = world > 1 or group is not None  # as GossipRound.coll
-        self.lo, self.hi, self.per = shard(self.n_nodes, world, rank)
-        m = self.hi - self.lo
-        assert x_init.shape[0] == m
-        self.N = N = x_init.shape[1]
+        super().__init__(adj, x_init, rank, world, group, device)
+        m, N = self.m, self.N
         self.alpha = float(alpha)
         self.seeds = [int(s) for s in seeds]
         self.layerwise = bool(layerwise)
-        self.device = device or x_init.device
         self._hip = encode is None
         self._encode, self._fold = encode, fold
-        self.cap = _up4(slot_cap) if slot_cap is not None else slot_capacity(N, self.alpha)
+        self.cap = up4(slot_cap) if slot_cap is not None else slot_capacity(N, self.alpha)
         self.x = x_init.contiguous().clone()
         self.out = torch.empty_like(self.x)
         self.counter = torch.zeros(m, N, dtype=torch.int32, device=self.device)
         if self._hip:
             from . import codec
-            self._mw, self._re = _up4(codec.mask_words(N)), _up4(codec.mt_rank_entries(N))
+            self._mw, self._re = up4(codec.mask_words(N)), up4(codec.mt_rank_entries(N))
             self._ws = codec.Workspace(self.device)
         else:
             self._mw = self._re = 0  # the injected fold rebuilds the masks from the seeds
         # a node's packed row: [count (int64), status, 0 | cap values | mask words | rank table]
-        self.row_words = W = HEADER + self.cap + self._mw + self._re
-        i32 = dict(dtype=torch.int32, device=self.device)
-        self.send = torch.zeros(self.per, W, **i32)
-        self.recv = torch.zeros(self.per * world, W, **i32) if self.coll else None
+        self._alloc_rows(HEADER + self.cap + self._mw + self._re)
         self._count = torch.zeros(max(1, self.per), dtype=torch.int64, device=self.device)
-        self.guard = torch.zeros(self.per * world, **i32)
-        cuda = self.device.type == "cuda"
-        self._guard_host = torch.zeros(self.per * world, dtype=torch.int32, pin_memory=cuda)
         self.weights = [mh_weights(adj, i) for i in range(self.lo, self.hi)]
         self._tabs = {}
-        self.round = 0
 
     # ---- views of the packed rows ---------------------------------------------------------------
-    def _rows(self):
-        """The rows the folds read: every node's after the all-gather, this rank's in place."""
-        return self.recv if self.coll else self.send
-
-    def _row(self, q):
-        return self.recv[q] if self.coll else self.send[q - self.lo]
-
     def _vals(self, rows):
         return rows[..., HEADER:HEADER + self.cap].view(torch.float32)
 
@@ -123,14 +99,13 @@ class SubSamplingRound:
         """``(seed, alpha, params)`` of node q's payload of the last round, in the wire dict's
         terms (any node after an all-gather, an owned one otherwise).  Reads the count: blocks."""
         row = self._row(q)
-        count = int(row[:2].view(torch.int64).item())
         return (self.seeds[q] + self.round - 1, self.alpha,
-                self._vals(row)[:min(count, self.cap)])
+                self._vals(row)[:min(self._count_of(row), self.cap)])
 
     # ---- the legs of a round --------------------------------------------------------------------
     def masks(self):
         """The owned nodes' masks of this round into their rows, one launch per phase."""
-        m = self.hi - self.lo
+        m = self.m
         if not self._hip or not m:
             return
         from . import codec
@@ -141,7 +116,7 @@ class SubSamplingRound:
 
     def gather(self):
         """Every owned node's ``x[mask]`` into its slot, the counters, the rows' headers."""
-        m = self.hi - self.lo
+        m = self.m
         if not m:
             return
         if not self._hip:
@@ -165,23 +140,14 @@ class SubSamplingRound:
             codec.mask_gather_nodes(self._tabs[key], self.N, self.cap)
         self.send[:m, :2].copy_(self._count[:m].view(torch.int32).view(m, 2))
 
-    def exchange(self):
-        """ONE all-gather of the packed rows; then the status words of every row, contiguous."""
-        if self.coll:
-            import torch.distributed as dist
-            dist.all_gather_into_tensor(self.recv, self.send, group=self.group)
-            self.guard.copy_(self.recv[:, 2])
-        else:
-            self.guard[:self.per].copy_(self.send[:, 2])
-
     def _dests(self):
         """Per owned node: (local, out, w_self, [(mask, rank_tab, vals, w)]) over the rows."""
-        rows = self._rows()
+        rows = self.rows
         dests = []
         for j, (nbrs, w, w_self) in enumerate(self.weights):
             pays = []
             for q, wq in zip(nbrs, w):
-                r = rows[q if self.coll else q - self.lo]
+                r = rows[q]
                 pays.append((self._masks(r), self._ranks(r), self._vals(r), wq))
             dests.append((self.x[j], self.out[j], w_self, pays))
         return dests
@@ -189,22 +155,17 @@ class SubSamplingRound:
     def fold(self):
         """Every owned node's Metro-Hastings fold into ``out``, behind the status words.  Returns
         the status words as the host sees them (one read, after the folds are enqueued)."""
-        m = self.hi - self.lo
-        cuda = self.device.type == "cuda"
-        self._guard_host.copy_(self.guard, non_blocking=cuda)
+        self._guard_to_host()
         ev = None
-        if cuda:
+        if self.device.type == "cuda":
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(self.device))
         if not self._hip:
             if not bool(self._guard_host.any()):
                 for j, (nbrs, w, w_self) in enumerate(self.weights):
-                    t = self.round
-                    pays = []
-                    for q in nbrs:
-                        row = self._row(q)
-                        count = int(row[:2].view(torch.int64).item())
-                        pays.append((self.seeds[q] + t, self.alpha, self._vals(row)[:count]))
+                    rows = [(q, self._row(q)) for q in nbrs]
+                    pays = [(self.seeds[q] + self.round, self.alpha,
+                             self._vals(row)[:self._count_of(row)]) for q, row in rows]
                     self._fold(self.x[j], pays, w, w_self, self.out[j])
             return self._guard_host
         from . import codec
@@ -242,12 +203,12 @@ class SubSamplingRound:
         mark("gather")
         self.exchange()
         mark("exchange")
-        status = self.fold()
+        self.fold()
         mark("fold")
-        bad = np.flatnonzero(status.numpy())
-        if len(bad):
+        bad = self._bad_nodes()
+        if bad:
             raise RuntimeError(
-                f"SubSampling round {self.round}: the masks of nodes {bad.tolist()} select more "
+                f"SubSampling round {self.round}: the masks of nodes {bad} select more "
                 f"than the slot's {self.cap} values; nothing was folded")
         self.x, self.out = self.out, self.x
         self.round += 1

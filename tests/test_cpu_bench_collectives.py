@@ -4,14 +4,10 @@
 codec.  Every rank must issue the identical sequence of collectives (a mismatch hangs RCCL), and
 the bench line's ``gossip_round`` / ``shard`` objects must carry the same keys at N = 2 as at
 N = 1 (VERDICT r4 next #8: the first multi-rank RCCL run is the driver's SCALE run)."""
-import os
-
-import numpy as np
-import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
+from tests.dist_harness import spawn_gloo
 from tests.test_cpu_gossip import _oracle_encode, _oracle_fold, _torch_combine, _torch_partial
 from tests.test_cpu_shard import OracleOps
 
@@ -65,37 +61,18 @@ def _legs(rank, world, d):
     return out
 
 
-def _worker(rank, world, port, q):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        with _Recorder() as rec:
-            out = _legs(rank, world, dist)
-        q.put((rank, rec.calls, {k: sorted(v) for k, v in out.items()}))
-    except Exception as e:  # noqa: BLE001 - reported to the parent instead of a queue timeout
-        import traceback
-        q.put((rank, None, traceback.format_exc() + repr(e)))
-    finally:
-        dist.destroy_process_group()
+def _worker(rank, world):
+    with _Recorder() as rec:
+        out = _legs(rank, world, dist)
+    return rec.calls, {k: sorted(v) for k, v in out.items()}
 
 
 def test_multi_rank_legs_issue_identical_collectives():
-    world = 2
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, 29740, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = sorted([q.get(timeout=300) for _ in procs], key=lambda t: t[0])
-    for p in procs:
-        p.join(timeout=60)
-    for rank, calls, keys in res:
-        assert calls is not None, keys
-    calls0, calls1 = res[0][1], res[1][1]
+    res = spawn_gloo(_worker, 2)
+    calls0, calls1 = res[0][0], res[1][0]
     assert len(calls0) > 0 and calls0 == calls1  # the same collectives, shapes, dtypes, ops
     names = {c[0] for c in calls0}
     assert {"all_gather_into_tensor", "reduce_scatter_tensor", "all_reduce", "barrier"} <= names
     # the N = 1 line's objects keep their keys at N = 2
     one = {k: sorted(v) for k, v in _legs(0, 1, None).items()}
-    assert res[0][2] == one and res[1][2] == one
+    assert res[0][1] == one and res[1][1] == one

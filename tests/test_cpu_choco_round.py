@@ -12,9 +12,9 @@ import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from tests import choco_round_ops as ops
+from tests.dist_harness import spawn_gloo
 
 
 def np_encode(x, x_hat, k):
@@ -163,26 +163,17 @@ def test_step_is_one_encode_one_collective_one_fold(monkeypatch):
 
 
 # ---- 2 and 3 ranks over gloo --------------------------------------------------------------------
-def _worker(rank, world, port, name, q):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from decentralizepy_amd.gossip import shard
-        from decentralizepy_amd.gossip_choco import ChocoRound
-        meta, arr = RUNS[RUN_IDS.index(name)]
-        lo, hi, per = shard(meta["nodes"], world, rank)
-        eng = ChocoRound(ops.run_adjacency(meta), torch.from_numpy(arr["x0"][lo:hi]),
-                         meta["alpha"], meta["step_size"], rank=rank, world=world,
-                         slot_cap=meta["slot_cap"], encode=np_encode, fold=np_fold)
-        assert eng.coll and eng.recv.shape[0] == per * world
-        drive(eng, meta, arr, lo=lo, every_payload=True)
-        q.put((rank, lo, hi, "ok"))
-    except BaseException as e:  # noqa: BLE001 - reported to the parent instead of a queue timeout
-        q.put((rank, None, None, repr(e)))
-        raise
-    finally:
-        dist.destroy_process_group()
+def _worker(rank, world, name):
+    from decentralizepy_amd.gossip import shard
+    from decentralizepy_amd.gossip_choco import ChocoRound
+    meta, arr = RUNS[RUN_IDS.index(name)]
+    lo, hi, per = shard(meta["nodes"], world, rank)
+    eng = ChocoRound(ops.run_adjacency(meta), torch.from_numpy(arr["x0"][lo:hi]),
+                     meta["alpha"], meta["step_size"], rank=rank, world=world,
+                     slot_cap=meta["slot_cap"], encode=np_encode, fold=np_fold)
+    assert eng.coll and eng.recv.shape[0] == per * world
+    drive(eng, meta, arr, lo=lo, every_payload=True)
+    return lo, hi
 
 
 @pytest.mark.parametrize("name,world", [("irr6", 2), ("regular16", 3), ("irr6", 3)])
@@ -191,20 +182,8 @@ def test_gloo_worlds_reproduce_the_reference(name, world):
     nn = RUNS[RUN_IDS.index(name)][0]["nodes"]
     if (name, world) == ("regular16", 3):
         assert shard(nn, 3, 2) == (12, 16, 6)  # 6 + 6 + 4: the last rank's block is padded
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = 29300 + (os.getpid() % 1000) + 7 * world
-    procs = [ctx.Process(target=_worker, args=(r, world, port, name, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=300) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    assert sorted(g[0] for g in got) == list(range(world))
-    for rank, lo, hi, msg in got:
-        assert msg == "ok", (rank, msg)
-    assert sum(hi - lo for _, lo, hi, _ in got) == nn
+    got = spawn_gloo(_worker, world, name)  # one result per rank; a failed drive() fails here
+    assert len(got) == world and sum(hi - lo for lo, hi in got) == nn
 
 
 # ---- the C entry points: every check is made on the host, before any device call ---------------

@@ -10,10 +10,9 @@ import os
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from tests import epidemic_ops as ops
+from tests.dist_harness import spawn_gloo
 
 EL_RUNS = ["el_d7", "el_d1", "el_d15"]
 
@@ -97,49 +96,24 @@ def test_numpy_engine_reproduces_the_reference(name):
         ops.check_round(meta, last, r, ref.x, received=ref.received_this_round if el else None)
 
 
-def _worker(rank, world, port, name, q):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        meta, last = ops.load(name)
-        eng = make_engine(meta, rank=rank, world=world, fold=np_fold)
-        assert eng.coll and eng.recv.shape == (eng.per * world, eng.stride)
-        run_and_check(eng, meta, last)
-        q.put((rank, eng.hi - eng.lo, eng.per, None))
-    except BaseException as e:  # noqa: BLE001 - reported to the parent instead of a queue timeout
-        q.put((rank, None, None, repr(e)))
-        raise
-    finally:
-        dist.destroy_process_group()
-
-
-def _spawn(target, world, args, port_base):
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = port_base + (os.getpid() % 1000)
-    procs = [ctx.Process(target=target, args=(r, world, port) + args + (q,)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = sorted(q.get(timeout=300) for _ in procs)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    return got
+def _worker(rank, world, name):
+    meta, last = ops.load(name)
+    eng = make_engine(meta, rank=rank, world=world, fold=np_fold)
+    assert eng.coll and eng.recv.shape == (eng.per * world, eng.stride)
+    run_and_check(eng, meta, last)
+    return eng.hi - eng.lo, eng.per
 
 
 def test_two_ranks_reproduce_the_reference():
     """gloo, world 2: the all-gather carries every model; 16 nodes split 8 + 8."""
-    got = _spawn(_worker, 2, ("el_d7",), 29300)
-    assert [(m, per, err) for _, m, per, err in got] == [(8, 8, None), (8, 8, None)]
+    assert spawn_gloo(_worker, 2, "el_d7") == [(8, 8), (8, 8)]
 
 
 def test_three_ranks_with_a_padded_last_rank_reproduce_the_reference():
     """Neither recorded graph pads over 2 ranks (16 and 6 nodes); over 3 ranks the 16 nodes
     split 6 + 6 + 4 and the last block of the all-gather is padded.  The degree-1 run: some
     nodes receive nothing."""
-    got = _spawn(_worker, 3, ("el_d1",), 31300)
-    assert [(m, per, err) for _, m, per, err in got] == [(6, 6, None), (6, 6, None), (4, 6, None)]
+    assert spawn_gloo(_worker, 3, "el_d1") == [(6, 6), (6, 6), (4, 6)]
 
 
 def test_two_ranks_with_a_padded_last_rank():
@@ -147,13 +121,12 @@ def test_two_ranks_with_a_padded_last_rank():
     against the node-by-node numpy engine."""
     from decentralizepy_amd.gossip import shard
     assert shard(5, 2, 1) == (3, 5, 3)
-    got = _spawn(_ring_worker, 2, (), 30300)
+    got = spawn_gloo(_ring_worker, 2)
     want = _ring_reference()
-    for rank, lo, xs in got:
-        assert lo is not None, xs
+    for lo, xs in got:
         for a, b in zip(xs, want):
             np.testing.assert_array_equal(a.view(np.uint32), b[lo:lo + len(a)].view(np.uint32))
-    assert [len(xs[0]) for _, _, xs in got] == [3, 2]
+    assert [len(xs[0]) for _, xs in got] == [3, 2]
 
 
 RING5 = [(0, 1), (1, 2), (2, 3), (3, 4), (4, 0), (0, 2)]
@@ -186,26 +159,17 @@ def _ring_reference(rounds=3):
     return out
 
 
-def _ring_worker(rank, world, port, q):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from decentralizepy_amd.gossip import shard
-        from decentralizepy_amd.gossip_epidemic import EpidemicRound
-        lo, hi, _ = shard(5, world, rank)
-        eng = EpidemicRound(_ring_adj(), torch.from_numpy(_ring_models()[lo:hi]), 1, 0,
-                            senders=_ring_senders, rank=rank, world=world, fold=np_fold)
-        xs = []
-        for _ in range(3):
-            eng.step()
-            xs.append(eng.x.numpy().copy())
-        q.put((rank, lo, xs))
-    except BaseException as e:  # noqa: BLE001
-        q.put((rank, None, repr(e)))
-        raise
-    finally:
-        dist.destroy_process_group()
+def _ring_worker(rank, world):
+    from decentralizepy_amd.gossip import shard
+    from decentralizepy_amd.gossip_epidemic import EpidemicRound
+    lo, hi, _ = shard(5, world, rank)
+    eng = EpidemicRound(_ring_adj(), torch.from_numpy(_ring_models()[lo:hi]), 1, 0,
+                        senders=_ring_senders, rank=rank, world=world, fold=np_fold)
+    xs = []
+    for _ in range(3):
+        eng.step()
+        xs.append(eng.x.numpy().copy())
+    return lo, xs
 
 
 def test_senders_override_is_honoured():

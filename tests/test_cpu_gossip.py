@@ -7,12 +7,11 @@ import os
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from oracle import fold as ofold
 from oracle import topk as otopk
 from tests import scenario
+from tests.dist_harness import spawn_gloo
 
 EDGES96 = os.path.join(scenario.GOLDEN, "96_regular.edges")
 EDGES16 = os.path.join(scenario.GOLDEN, "regular_16.edges")
@@ -87,23 +86,17 @@ def test_single_rank_round_matches_direct_simulation():
         np.testing.assert_array_equal(eng.x.numpy().view(np.uint32), ref_x.view(np.uint32))
 
 
-def _worker(rank, world, port, n, path, q):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from decentralizepy_amd.gossip import GossipRound, read_edges, shard
-        adj = read_edges(path)
-        x = _models(len(adj), n)
-        lo, hi, _ = shard(len(adj), world, rank)
-        eng = GossipRound(adj, x[lo:hi], 0.05, rank=rank, world=world, encode=_oracle_encode,
-                          fold=_oracle_fold)
-        for r in range(2):
-            _train(eng, r)
-            eng.step()
-        q.put((rank, lo, eng.x.numpy().copy()))
-    finally:
-        dist.destroy_process_group()
+def _worker(rank, world, n, path):
+    from decentralizepy_amd.gossip import GossipRound, read_edges, shard
+    adj = read_edges(path)
+    x = _models(len(adj), n)
+    lo, hi, _ = shard(len(adj), world, rank)
+    eng = GossipRound(adj, x[lo:hi], 0.05, rank=rank, world=world, encode=_oracle_encode,
+                      fold=_oracle_fold)
+    for r in range(2):
+        _train(eng, r)
+        eng.step()
+    return lo, eng.x.numpy().copy()
 
 
 @pytest.mark.parametrize("path,n", [(EDGES16, 1500), (EDGES96, 600)])
@@ -115,17 +108,7 @@ def test_two_rank_round_equals_single_rank(path, n):
     for r in range(2):
         _train(single, r)
         single.step()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = 29500 + (os.getpid() % 1000)
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, n, path, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=300) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    for rank, lo, xs in got:
+    for lo, xs in spawn_gloo(_worker, 2, n, path):
         np.testing.assert_array_equal(xs.view(np.uint32),
                                       single.x.numpy()[lo:lo + xs.shape[0]].view(np.uint32))
 
@@ -140,35 +123,26 @@ def _torch_combine(x, b, a, c, out):
     out.copy_(x * (torch.tensor(c, dtype=torch.float32) - b) + a)
 
 
-def _rs_worker(rank, world, port, n, path, q, skew=False):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from decentralizepy_amd.gossip import GossipRound, read_edges, shard
-        adj = read_edges(path)
-        x = _models(len(adj), n)
-        lo, hi, per = shard(len(adj), world, rank)
-        k = round(0.05 * n)
-        # an emulated budget one byte below ONE payload: neither the all-gathered payloads nor
-        # the peer exchange's fit, auto picks the reduce-scatter, one destination node per group
-        budget = k * 8 - 1
-        if skew:  # rank 1 alone would fit the all-gather: the ranks must still agree (MIN)
-            budget += rank * 10 ** 12
-        eng = GossipRound(adj, x[lo:hi], 0.05, rank=rank, world=world, encode=_oracle_encode,
-                          fold=_oracle_fold, hbm_budget=budget, partial=_torch_partial,
-                          combine=_torch_combine)
-        assert eng.exchange_mode == "reduce_scatter" and eng.recv_idx is None
-        assert eng.rs_group == 1
-        for r in range(2):
-            _train(eng, r)
-            eng.step()
-        q.put((rank, lo, eng.x.numpy().copy()))
-    except Exception as e:  # noqa: BLE001 - reported to the parent instead of a queue timeout
-        q.put((rank, None, repr(e)))
-        raise
-    finally:
-        dist.destroy_process_group()
+def _rs_worker(rank, world, n, path, skew):
+    from decentralizepy_amd.gossip import GossipRound, read_edges, shard
+    adj = read_edges(path)
+    x = _models(len(adj), n)
+    lo, hi, per = shard(len(adj), world, rank)
+    k = round(0.05 * n)
+    # an emulated budget one byte below ONE payload: neither the all-gathered payloads nor
+    # the peer exchange's fit, auto picks the reduce-scatter, one destination node per group
+    budget = k * 8 - 1
+    if skew:  # rank 1 alone would fit the all-gather: the ranks must still agree (MIN)
+        budget += rank * 10 ** 12
+    eng = GossipRound(adj, x[lo:hi], 0.05, rank=rank, world=world, encode=_oracle_encode,
+                      fold=_oracle_fold, hbm_budget=budget, partial=_torch_partial,
+                      combine=_torch_combine)
+    assert eng.exchange_mode == "reduce_scatter" and eng.recv_idx is None
+    assert eng.rs_group == 1
+    for r in range(2):
+        _train(eng, r)
+        eng.step()
+    return lo, eng.x.numpy().copy()
 
 
 @pytest.mark.parametrize("path,n,skew", [(EDGES16, 1500, False), (EDGES96, 600, False),
@@ -185,19 +159,7 @@ def test_reduce_scatter_round_matches_within_tolerance(path, n, skew):
     for r in range(2):
         _train(single, r)
         single.step()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = 29700 + (os.getpid() % 1000) + (7 if skew else 0)
-    procs = [ctx.Process(target=_rs_worker, args=(r, 2, port, n, path, q, skew))
-             for r in range(2)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=300) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    for rank, lo, xs in got:
-        assert lo is not None, xs
+    for lo, xs in spawn_gloo(_rs_worker, 2, n, path, skew):
         ref = single.x.numpy()[lo:lo + xs.shape[0]]
         np.testing.assert_allclose(xs, ref, rtol=1e-5, atol=1e-6)
 
@@ -243,28 +205,19 @@ def test_guarded_round_reruns_a_missed_encode(miss_round):
     assert state["reruns"] == 1
 
 
-def _peer_worker(rank, world, port, n, path, q, budget):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from decentralizepy_amd.gossip import GossipRound, read_edges, shard
-        adj = read_edges(path)
-        x = _models(len(adj), n)
-        lo, hi, _ = shard(len(adj), world, rank)
-        kw = dict(exchange="peer") if budget is None else dict(hbm_budget=budget)
-        eng = GossipRound(adj, x[lo:hi], 0.05, rank=rank, world=world, encode=_oracle_encode,
-                          fold=_oracle_fold, **kw)
-        assert eng.exchange_mode == "peer" and eng.recv_idx is None
-        for r in range(2):
-            _train(eng, r)
-            eng.step()
-        q.put((rank, lo, eng.x.numpy().copy(), eng._peer_n_recv))
-    except Exception as e:  # noqa: BLE001 - reported to the parent instead of a queue timeout
-        q.put((rank, None, repr(e), 0))
-        raise
-    finally:
-        dist.destroy_process_group()
+def _peer_worker(rank, world, n, path, budget):
+    from decentralizepy_amd.gossip import GossipRound, read_edges, shard
+    adj = read_edges(path)
+    x = _models(len(adj), n)
+    lo, hi, _ = shard(len(adj), world, rank)
+    kw = dict(exchange="peer") if budget is None else dict(hbm_budget=budget)
+    eng = GossipRound(adj, x[lo:hi], 0.05, rank=rank, world=world, encode=_oracle_encode,
+                      fold=_oracle_fold, **kw)
+    assert eng.exchange_mode == "peer" and eng.recv_idx is None
+    for r in range(2):
+        _train(eng, r)
+        eng.step()
+    return lo, eng.x.numpy().copy(), eng._peer_n_recv
 
 
 @pytest.mark.parametrize("path,n,world,auto", [(EDGES16, 1500, 2, False), (EDGES96, 600, 2, False),
@@ -284,19 +237,7 @@ def test_peer_exchange_round_equals_single_rank(path, n, world, auto):
     _, _, per = shard(len(adj), world, 0)
     k = round(0.05 * n)
     budget = per * world * k * 8 - 1 if auto else None  # one byte short of the all-gather
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = 29300 + (os.getpid() % 1000) + 11 * world + (5 if auto else 0)
-    procs = [ctx.Process(target=_peer_worker, args=(r, world, port, n, path, q, budget))
-             for r in range(world)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=300) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    for rank, lo, xs, n_recv in got:
-        assert lo is not None, xs
+    for lo, xs, n_recv in spawn_gloo(_peer_worker, world, n, path, budget):
         assert n_recv <= per * (world - 1)
         np.testing.assert_array_equal(xs.view(np.uint32),
                                       single.x.numpy()[lo:lo + xs.shape[0]].view(np.uint32))

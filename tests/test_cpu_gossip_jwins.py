@@ -6,10 +6,9 @@ import os
 
 import numpy as np
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from tests import scenario
+from tests.dist_harness import spawn_gloo
 from tests.jwins_ops import OracleJwinsOps, coeff_len, direct_round_nodes
 
 EDGES16 = os.path.join(scenario.GOLDEN, "regular_16.edges")
@@ -69,23 +68,14 @@ def test_alpha_draws_cover_full_and_partial_shares():
     assert any(a >= 0.5 for a in seen) and any(a < 0.5 for a in seen)
 
 
-def _worker(rank, world, port, n, q):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from decentralizepy_amd.gossip import read_edges, shard
-        adj = read_edges(EDGES16)
-        x = _x(16, n)
-        lo, hi, _ = shard(16, world, rank)
-        eng = _engine(adj, x[lo:hi], rank=rank, world=world)
-        _run(eng, 3, n)
-        q.put((rank, lo, eng.x.numpy().copy(), eng.acc.numpy().copy()))
-    except Exception as e:  # noqa: BLE001 - reported to the parent instead of a queue timeout
-        q.put((rank, None, repr(e), None))
-        raise
-    finally:
-        dist.destroy_process_group()
+def _worker(rank, world, n):
+    from decentralizepy_amd.gossip import read_edges, shard
+    adj = read_edges(EDGES16)
+    x = _x(16, n)
+    lo, hi, _ = shard(16, world, rank)
+    eng = _engine(adj, x[lo:hi], rank=rank, world=world)
+    _run(eng, 3, n)
+    return lo, eng.x.numpy().copy(), eng.acc.numpy().copy()
 
 
 def test_two_rank_round_equals_single_rank():
@@ -95,18 +85,7 @@ def test_two_rank_round_equals_single_rank():
     x = _x(16, n)
     single = _engine(adj, x)
     _run(single, 3, n)
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = 29900 + (os.getpid() % 1000)
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, n, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=300) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    for rank, lo, xs, acc in got:
-        assert lo is not None, xs
+    for lo, xs, acc in spawn_gloo(_worker, 2, n):
         np.testing.assert_array_equal(xs.view(np.uint32),
                                       single.x.numpy()[lo:lo + xs.shape[0]].view(np.uint32))
         np.testing.assert_array_equal(acc.view(np.uint32),

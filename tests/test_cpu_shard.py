@@ -2,15 +2,12 @@
 the oracle standing in for the HIP steps gives exactly the one-tensor encode of the reference rule
 (k largest |x - x0|, lowest-index ties), payload and counter, on every rank — including ties that
 straddle the shard boundary.  The device steps are covered by tests/test_gpu_shard.py."""
-import os
-
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from oracle import topk as otopk
+from tests.dist_harness import spawn_gloo
 
 
 class OracleOps:
@@ -49,48 +46,32 @@ def _inputs(n, ties):
     return x, x0
 
 
-def _worker(rank, world, port, n, k, ties, out_q, fp16=False):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from decentralizepy_amd.shard import sharded_topk_encode
-        x, x0 = _inputs(n, ties)
-        bounds = np.linspace(0, n, world + 1).astype(int)
-        lo, hi = int(bounds[rank]), int(bounds[rank + 1])
-        cnt = torch.zeros(hi - lo, dtype=torch.int32)
-        from decentralizepy_amd.shard import sharded_replace
-        ops = OracleOps()
-        idx, val = sharded_topk_encode(x[lo:hi].contiguous(), x0[lo:hi].contiguous(), k, lo,
-                                       counter=cnt, ops=ops, val_fp16=fp16)
-        if fp16:
-            out_q.put((rank, idx.numpy(), val.numpy(), lo, cnt.numpy(), None))
-            return
-        # decode of the global payload into this rank's slice: most entries lie outside it
-        dec = sharded_replace(x0[lo:hi].contiguous(), lo, idx, val, ops=ops)
-        out_q.put((rank, idx.numpy(), val.numpy(), lo, cnt.numpy(), dec.numpy()))
-    finally:
-        dist.destroy_process_group()
+def _worker(rank, world, n, k, ties, fp16=False):
+    from decentralizepy_amd.shard import sharded_replace, sharded_topk_encode
+    x, x0 = _inputs(n, ties)
+    bounds = np.linspace(0, n, world + 1).astype(int)
+    lo, hi = int(bounds[rank]), int(bounds[rank + 1])
+    cnt = torch.zeros(hi - lo, dtype=torch.int32)
+    ops = OracleOps()
+    idx, val = sharded_topk_encode(x[lo:hi].contiguous(), x0[lo:hi].contiguous(), k, lo,
+                                   counter=cnt, ops=ops, val_fp16=fp16)
+    if fp16:
+        return idx.numpy(), val.numpy(), lo, cnt.numpy(), None
+    # decode of the global payload into this rank's slice: most entries lie outside it
+    dec = sharded_replace(x0[lo:hi].contiguous(), lo, idx, val, ops=ops)
+    return idx.numpy(), val.numpy(), lo, cnt.numpy(), dec.numpy()
 
 
 @pytest.mark.parametrize("world,ties", [(2, False), (2, True), (3, True)])
 def test_sharded_topk_equals_whole_tensor_encode(world, ties):
     n, k = 30_000, 1_500
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = 29650 + world * 2 + int(ties)
-    procs = [ctx.Process(target=_worker, args=(r, world, port, n, k, ties, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = [q.get(timeout=120) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
+    res = spawn_gloo(_worker, world, n, k, ties, timeout=120)
     x, x0 = _inputs(n, ties)
     o_cnt = np.zeros(n, dtype=np.int32)
     oi, ov = otopk.encode(x.numpy(), x0.numpy(), None, otopk.ACC_NONE, k, counter=o_cnt)
     full_cnt = np.zeros(n, dtype=np.int32)
     full_dec = np.full(n, np.nan, dtype=np.float32)
-    for rank, idx, val, lo, cnt, dec in res:
+    for idx, val, lo, cnt, dec in res:
         np.testing.assert_array_equal(idx, oi)
         np.testing.assert_array_equal(val.view(np.uint32), ov.view(np.uint32))
         full_cnt[lo:lo + cnt.shape[0]] = cnt
@@ -127,27 +108,18 @@ def _fake_dwt_rank_part(xb, x0b, first, n, level, t_lo, t_hi, cx, cd, accumulate
 _DW, _IW = 128, 4096
 
 
-def _wavelet_worker(rank, world, port, n, out_q):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from decentralizepy_amd import shard
-        shard.dwt_rank_part = _fake_dwt_rank_part
-        shard._DEVICE_ONLY = False
-        assert shard.tile_widths() == (_DW, _IW)
-        g = torch.Generator().manual_seed(n)
-        x = torch.randn(n, generator=g)
-        x0 = x - 0.01 * torch.randn(n, generator=g)
-        sl = shard.wavelet_slice(n, 4, world, rank, _DW, _IW)
-        cx, cd = shard.sharded_wavedec(x[sl["lo"]:sl["hi"]].contiguous(),
-                                       x0[sl["lo"]:sl["hi"]].contiguous(), n, 4)
-        out_q.put((rank, cx.numpy(), cd.numpy()))
-    except Exception as e:  # surface the failure instead of a queue timeout
-        out_q.put((rank, repr(e), None))
-        raise
-    finally:
-        dist.destroy_process_group()
+def _wavelet_worker(rank, world, n):
+    from decentralizepy_amd import shard
+    shard.dwt_rank_part = _fake_dwt_rank_part
+    shard._DEVICE_ONLY = False
+    assert shard.tile_widths() == (_DW, _IW)
+    g = torch.Generator().manual_seed(n)
+    x = torch.randn(n, generator=g)
+    x0 = x - 0.01 * torch.randn(n, generator=g)
+    sl = shard.wavelet_slice(n, 4, world, rank, _DW, _IW)
+    cx, cd = shard.sharded_wavedec(x[sl["lo"]:sl["hi"]].contiguous(),
+                                   x0[sl["lo"]:sl["hi"]].contiguous(), n, 4)
+    return cx.numpy(), cd.numpy()
 
 
 @pytest.mark.parametrize("world,n", [(2, 100_003), (3, 100_003), (4, 16_484)])
@@ -155,22 +127,13 @@ def test_sharded_wavedec_exchange(world, n):
     """(4, 16484): ranks 2 and 3 hold empty slices (5 inverse tiles over 4 ranks at 2 each), so
     the tail forward tiles belong to rank 2's predecessor, the slice holding element n - 1."""
     from oracle import wavelet as owav
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = 29710 + world
-    procs = [ctx.Process(target=_wavelet_worker, args=(r, world, port, n, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = [q.get(timeout=180) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
+    res = spawn_gloo(_wavelet_worker, world, n, timeout=180)
     g = torch.Generator().manual_seed(n)
     x = torch.randn(n, generator=g)
     x0 = x - 0.01 * torch.randn(n, generator=g)
     ref_x = owav.wavedec_array(x.numpy(), 4)
     ref_d = owav.wavedec_array(x.numpy() - x0.numpy(), 4)
-    for rank, cx, cd in res:
-        assert cd is not None, f"rank {rank} failed: {cx}"
+    for cx, cd in res:
         np.testing.assert_array_equal(cx.view(np.uint32), ref_x.view(np.uint32))
         np.testing.assert_array_equal(cd.view(np.uint32), ref_d.view(np.uint32))
 
@@ -213,19 +176,10 @@ def test_sharded_topk_fp16_values(world, k):
     all-gather (10 bytes per candidate) and the merge: the whole-tensor payload with torch.half
     values on every rank.  Odd k: the value section is padded to 4 bytes in the packed row."""
     n = 30_000
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = 29690 + world + (k % 2) * 5
-    procs = [ctx.Process(target=_worker, args=(r, world, port, n, k, True, q, True))
-             for r in range(world)]
-    for p in procs:
-        p.start()
-    res = [q.get(timeout=120) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
+    res = spawn_gloo(_worker, world, n, k, True, True, timeout=120)
     x, x0 = _inputs(n, True)
     oi, ov = otopk.encode(x.numpy(), x0.numpy(), None, otopk.ACC_NONE, k)
-    for rank, idx, val, lo, cnt, _ in res:
+    for idx, val, lo, cnt, _ in res:
         assert val.dtype == np.float16
         np.testing.assert_array_equal(idx, oi)
         np.testing.assert_array_equal(val.view(np.uint16),

@@ -5,14 +5,12 @@ HIP kernels, against a direct node-by-node simulation with ``OracleNode`` (one n
 device path is covered by tests/test_gpu_subsampling_round.py, which shares the helpers here."""
 import ctypes
 import math
-import os
 
 import numpy as np
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from tests import subsampling_ops as sops
+from tests.dist_harness import spawn_gloo
 
 # 6 nodes, degrees 3 3 2 3 3 2: a ring with two chords
 EDGES6 = [(0, 1), (1, 2), (2, 3), (3, 4), (4, 5), (5, 0), (0, 3), (1, 4)]
@@ -177,29 +175,20 @@ def test_small_slot_raises_and_keeps_the_models():
     np.testing.assert_array_equal(eng.x.numpy().view(np.uint32), x.numpy().view(np.uint32))
 
 
-def _worker(rank, world, port, n, alpha, q):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from decentralizepy_amd.gossip import shard
-        from decentralizepy_amd.gossip_subsampling import SubSamplingRound
-        adj = adjacency(5, EDGES5)
-        x = models(5, n)
-        lo, hi, _ = shard(5, world, rank)
-        eng = SubSamplingRound(adj, x[lo:hi], alpha, SEEDS[:5], rank=rank, world=world,
-                               encode=np_encode, fold=np_fold)
-        res = []
-        for _ in range(3):
-            eng.step()
-            res.append((eng.x.numpy().copy(), eng.counter.numpy().copy(),
-                        [eng.payload(p)[2].numpy().copy() for p in range(5)]))
-        q.put((rank, lo, res))
-    except Exception as e:  # noqa: BLE001 - reported to the parent instead of a queue timeout
-        q.put((rank, None, repr(e)))
-        raise
-    finally:
-        dist.destroy_process_group()
+def _worker(rank, world, n, alpha):
+    from decentralizepy_amd.gossip import shard
+    from decentralizepy_amd.gossip_subsampling import SubSamplingRound
+    adj = adjacency(5, EDGES5)
+    x = models(5, n)
+    lo, hi, _ = shard(5, world, rank)
+    eng = SubSamplingRound(adj, x[lo:hi], alpha, SEEDS[:5], rank=rank, world=world,
+                           encode=np_encode, fold=np_fold)
+    res = []
+    for _ in range(3):
+        eng.step()
+        res.append((eng.x.numpy().copy(), eng.counter.numpy().copy(),
+                    [eng.payload(p)[2].numpy().copy() for p in range(5)]))
+    return lo, res
 
 
 def test_two_rank_round_equals_single_rank():
@@ -216,18 +205,7 @@ def test_two_rank_round_equals_single_rank():
         check_round(single, ref)
         want.append((single.x.numpy().copy(), single.counter.numpy().copy(),
                      [single.payload(p)[2].numpy().copy() for p in range(5)]))
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = 29100 + (os.getpid() % 1000)
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, n, alpha, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=300) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    for rank, lo, res in got:
-        assert lo is not None, res
+    for lo, res in spawn_gloo(_worker, 2, n, alpha):
         for (xs, cs, pays), (wx, wc, wpays) in zip(res, want):
             m = xs.shape[0]
             np.testing.assert_array_equal(xs.view(np.uint32), wx[lo:lo + m].view(np.uint32))

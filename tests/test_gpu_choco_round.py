@@ -5,13 +5,13 @@ the restatement and the three-call sequence it replaces (DPZ_EW_ADD, the zero-ba
 gossip_choco.py) against the runs recorded from the reference and the per-node plugin's device
 sequence.  Sizes: one element, around a float4, the edges of the compaction chunk / the fold tile,
 several of them with a ragged tail."""
-import socket
-
 import numpy as np
 import pytest
 import torch
 
+from decentralizepy_amd.gossip_round import up4
 from tests import choco_round_ops as ops
+from tests.dist_harness import rccl_loopback
 from tests.test_cpu_choco_round import RUN_IDS, RUNS, drive
 
 pytestmark = pytest.mark.gpu
@@ -20,15 +20,11 @@ FILL = 0x5A5A5A5A
 HEADER = 4
 
 
-def _up4(v):
-    return -(-v // 4) * 4
-
-
 def _rows(dev, data, aligned):
     """Device rows of the fp32 matrix ``data``: 16-byte aligned rows with prefilled padding, or
     packed rows (unaligned when the width is no multiple of 4).  Returns (view, backing)."""
     m, n = data.shape
-    back = torch.full((m, _up4(n) + 4 if aligned else n), 7.0, dtype=torch.float32, device=dev)
+    back = torch.full((m, up4(n) + 4 if aligned else n), 7.0, dtype=torch.float32, device=dev)
     back[:, :n] = torch.from_numpy(data).to(dev)
     return back[:, :n], back
 
@@ -74,7 +70,7 @@ def test_encode_nodes_equals_topk_threshold(dev, which, aligned):
     ws = codec.Workspace(dev)
     for k in sorted({1, max(1, round(0.05 * n)), n}):
         x, xh = _encode_data(n, k, C, seed=n + k)
-        cap = _up4(n)
+        cap = up4(n)
         tx, th, rows = _run_encode(dev, x, xh, k, cap, aligned)
         if not aligned and n % 4:
             assert tx[1].data_ptr() % 16
@@ -186,7 +182,7 @@ def _expected(case, step, reverse=False):
 def _device_case(dev, case, aligned=True):
     from decentralizepy_amd import codec
     pays, x, xh, s, lists, weights, own, w_self, _ = case
-    cap = _up4(max(len(i) for i, _ in pays)) + 4
+    cap = up4(max(len(i) for i, _ in pays)) + 4
     rows = torch.full((len(pays), HEADER + 2 * cap), FILL, dtype=torch.int32, device=dev)
     host = rows.cpu().numpy()
     for p, (idx, vals) in enumerate(pays):  # the slots past the count keep the fill: never read
@@ -309,18 +305,8 @@ def test_step_launch_count_is_independent_of_the_node_count(dev):
 
 @pytest.fixture
 def rccl_group(dev):
-    import torch.distributed as dist
-    if dist.is_initialized():
-        pytest.skip("a process group already exists in this process")
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1,
-                            device_id=dev)
-    try:
-        yield dist.group.WORLD
-    finally:
-        dist.destroy_process_group()
+    with rccl_loopback(dev) as group:
+        yield group
 
 
 def test_engine_through_rccl_equals_in_place(dev, rccl_group):

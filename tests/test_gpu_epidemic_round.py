@@ -4,13 +4,12 @@ for bit on the staged and the direct path, and the engines of decentralizepy_amd
 against the runs recorded from the unmodified reference (tests/golden/epidemic.json).  Sizes: one
 element, less than and exactly one 16-byte column, the tile's edges, several tiles with a ragged
 tail; 2, 16 and 17 source rows (one tile width each side of the 1024 / 512 step)."""
-import socket
-
 import numpy as np
 import pytest
 import torch
 
 from tests import epidemic_ops as ops
+from tests.dist_harness import rccl_loopback
 from tests.test_cpu_epidemic_round import EL_RUNS, make_engine, run_and_check
 
 pytestmark = pytest.mark.gpu
@@ -245,18 +244,8 @@ def test_senders_override_on_the_device(dev):
 
 @pytest.fixture
 def rccl_group(dev):
-    import torch.distributed as dist
-    if dist.is_initialized():
-        pytest.skip("a process group already exists in this process")
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1,
-                            device_id=dev)
-    try:
-        yield dist.group.WORLD
-    finally:
-        dist.destroy_process_group()
+    with rccl_loopback(dev) as group:
+        yield group
 
 
 def test_engines_through_rccl_equal_in_place(dev, rccl_group):

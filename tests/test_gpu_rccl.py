@@ -6,11 +6,11 @@ all_gather_into_tensor, the over-HBM packed reduce_scatter_tensor, the JWINS var
 all-gather, the sharded top-k's candidate all-gather and the sharded DWT's halo / owned-range
 all-gathers — on device buffers; every result must equal the same engine run without a group
 bit-for-bit."""
-import socket
-
 import numpy as np
 import pytest
 import torch
+
+from tests.dist_harness import rccl_loopback
 
 pytestmark = pytest.mark.gpu
 
@@ -18,18 +18,9 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def rccl_group(dev):
     import torch.distributed as dist
-    if dist.is_initialized():
-        pytest.skip("a process group already exists in this process")
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1,
-                            device_id=dev)
-    assert dist.get_backend() == "nccl"
-    try:
-        yield dist.group.WORLD
-    finally:
-        dist.destroy_process_group()
+    with rccl_loopback(dev) as group:
+        assert dist.get_backend() == "nccl"
+        yield group
 
 
 def _bits(t):

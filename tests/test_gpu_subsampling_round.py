@@ -4,13 +4,12 @@ bit, and the engine (decentralizepy_amd/gossip_subsampling.py) against the node-
 ``OracleNode`` simulation of tests/test_cpu_subsampling_round.py.  Sizes: one element, one state
 block, the chunk edges (65536 elements a chunk), several chunks with a ragged tail, and one past
 256 chunks (the coarse launch)."""
-import socket
-
 import numpy as np
 import pytest
 import torch
 
 from tests import subsampling_ops as ops
+from tests.dist_harness import rccl_loopback
 from tests.test_cpu_subsampling_round import (EDGES6, SEEDS, adjacency, check_round, models,
                                               oracle_rounds, star)
 
@@ -240,18 +239,8 @@ def test_engine_small_slot_raises_and_keeps_the_models(dev, six_nodes):
 
 @pytest.fixture
 def rccl_group(dev):
-    import torch.distributed as dist
-    if dist.is_initialized():
-        pytest.skip("a process group already exists in this process")
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1,
-                            device_id=dev)
-    try:
-        yield dist.group.WORLD
-    finally:
-        dist.destroy_process_group()
+    with rccl_loopback(dev) as group:
+        yield group
 
 
 def test_engine_through_rccl_equals_in_place(dev, six_nodes, rccl_group):
