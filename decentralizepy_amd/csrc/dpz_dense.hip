@@ -1,6 +1,6 @@
 // Dense folds of a round's nodes in one launch (decentralizepy_amd/gossip_epidemic.py): every
 // payload is a full model, so a receiver's fold is a weighted sum over whole source rows, in the
-// fp32 order of the dense-payload DPZ_FOLD_SELF form of dpz_decode_average (dpz_fold.hip):
+// fp32 order of the dense-payload DPZ_FOLD_SELF form of dpz_decode_average (dpz_fold_tile.hip fold_kernel):
 //   t = fl(v_0 w_0);  t = fl(t + fl(v_i w_i)) in list order;  out = fl(t + fl(local w_self)),
 // products and sums rounded separately (-ffp-contract=off), and a receiver with an empty list
 // gets a bitwise copy of its own row.

@@ -1,6 +1,6 @@
 // Replace-only decode of ONE sparse payload (reference sharing/PartialModel.py:257-303,
 // `T = cat(local); T[idx] = params`), as a device function on payload-entry chunks, shared by the
-// standalone replace kernel (dpz_fold.hip) and the encoder's co-scheduled decode (a replace job
+// standalone replace kernel (dpz_fold_patch.hip) and the encoder's co-scheduled decode (a replace job
 // carried by the latency-bound top-k kernels in blocks of their own, dpz_topk_sampled.hip).
 //
 // Chunk c owns payload entries [RP_E c, RP_E c + RP_E) and the element range from its first
@@ -198,7 +198,7 @@ __device__ __forceinline__ void replace_block(const ReplaceJob& j, int64_t p) {
   rp_stream(j, c, lane, ch);
 }
 
-// host: the standalone replace kernel over chunks [j.c0, j.c1) (dpz_fold.hip)
+// host: the standalone replace kernel over chunks [j.c0, j.c1) (dpz_fold_patch.hip)
 int launch_replace(const ReplaceJob& j, hipStream_t st);
 
 }  // namespace dpz

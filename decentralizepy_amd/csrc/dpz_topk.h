@@ -352,7 +352,7 @@ static inline int64_t mask_words(int64_t n) { return (n + 31) >> 5; }
 int sliced_from_idx(const EncodeArgs& a, const uint32_t* guard = nullptr);
 // the fold base can ride on the pipelined filter: aligned, no accumulation, x0 given
 bool fused_foldbase_ok(const EncodeArgs& a, bool vec);
-// base_out[j] = fb.of(x[j]) as its own launch (dpz_fold.hip)
+// base_out[j] = fb.of(x[j]) as its own launch (dpz_fold_patch.hip)
 int launch_fold_base(const float* x, int64_t n, const FoldBase& fb, float* out, hipStream_t st);
 
 // dpz_topk_exact.hip / dpz_topk_sampled.hip

@@ -320,6 +320,28 @@ int dpz_decode_average(const float* local, int64_t n, int n_payloads, const int3
                        const float* const* vals, const int64_t* k, const float* w, float w_self,
                        int flags, float* out, void* ws, size_t ws_bytes, dpz_stream_t stream);
 
+/* Diagnostic: the kernel dpz_decode_average selects for ONE group of n_payloads <= 16 payloads,
+ * computed on the host with no device call (a CPU test pins the selection thresholds).  k / w:
+ * the group's sizes and weights (w may be NULL), dense[i] != 0: payload i is dense (NULL: none);
+ * flags: the call's DPZ_FOLD_* flags; fresh: the group starts the total (the first group of a
+ * call without DPZ_FOLD_ACCUMULATE); aligned: local, out and every dense payload are 16-byte
+ * aligned.  plan_out[DPZ_FOLD_PLAN_INTS] = { engine, vec (float4 kernels), epl (walk: elements
+ * per lane), dist (walk groups: 1 / 3 groups ahead), win (walk groups: 64 / 128-entry windows),
+ * ept (merge: elements per thread), eqw (merge: equal weights), offsets (the tile-offsets
+ * pre-pass runs first), chains (classic: the hit-chain path may run) }.                        */
+#define DPZ_FOLD_ENGINE_NONE 0        /* nothing to launch                                      */
+#define DPZ_FOLD_ENGINE_CLASSIC 1
+#define DPZ_FOLD_ENGINE_GROUP 2       /* the 4-slot group kernel                                */
+#define DPZ_FOLD_ENGINE_WALK 4        /* 1..4 payloads                                          */
+#define DPZ_FOLD_ENGINE_WALK_GROUPS 5 /* 5..16 payloads                                         */
+#define DPZ_FOLD_ENGINE_MERGE 8
+#define DPZ_FOLD_ENGINE_REPLACE 9     /* one sparse payload replaced / added                    */
+#define DPZ_FOLD_ENGINE_PATCH1 10     /* DPZ_FOLD_BASE_READY, one payload                       */
+#define DPZ_FOLD_ENGINE_PATCH 11      /* DPZ_FOLD_BASE_READY, 2..16 payloads                    */
+#define DPZ_FOLD_PLAN_INTS 9
+int dpz_debug_fold_plan(int64_t n, int n_payloads, const int64_t* k, const int* dense,
+                        const float* w, int flags, int fresh, int aligned, int* plan_out);
+
 /* Replace decode of a GLOBAL payload into one rank's slice of a model sharded over ranks
  * (SURVEY §8e "one tensor, decode: no collective"; reference sharing/PartialModel.py:292-295
  * `T[idx] = params` restricted to the slice): local / out hold global elements

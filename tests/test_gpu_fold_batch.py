@@ -1,4 +1,4 @@
-"""GPU: dpz_decode_average_batch's one-launch path (dpz_fold.hip fold_walk_batch_kernel: the plain
+"""GPU: dpz_decode_average_batch's one-launch path (dpz_fold_walk.hip fold_walk_batch_kernel: the plain
 Metro-Hastings folds of many nodes, <= 4 sparse payloads each, in one launch per 22 nodes) is
 bit-exact against the oracle's fold of each node (reference sharing/Sharing.py:156-190 over
 PartialModel payloads, PartialModel.py:257-303) — across launch boundaries, mixed payload counts

@@ -1,4 +1,4 @@
-"""GPU: the merge fold (csrc/dpz_fold.hip fold_merge_kernel: a group of 5..16 sparse payloads
+"""GPU: the merge fold (csrc/dpz_fold_merge.hip fold_merge_kernel: a group of 5..16 sparse payloads
 merged per tile through an LDS hit mask; the JWINS receive, reference sharing/JWINS/Wavelet.py:
 269-309, and the Metro-Hastings fold of Sharing.py:156-190) is bit-exact with the oracle's fp32
 fold: equal and unequal weights, the server form (no self term), a zero base, the result also

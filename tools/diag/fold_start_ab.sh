@@ -1,6 +1,9 @@
 #!/bin/bash
 # DPZ_WALK_GUESS was removed after the A/B (profiles/r05_fold_start_ab.txt): build lib_guess from
 # commit ff7398b (tools/diag/build_variant.sh guess "-DDPZ_WALK_GUESS=1" ff7398b) to re-run it.
+# DPZ_WALK4_LOCKSTEP / DPZ_WALK4_L_FIRST (and the groups kernel's DPZ_WALKG_* twins) were removed
+# after their A/B too (profiles/r04_c4_round_ab.jsonl): build lib_ls / lib_lf / lib_lslf from commit
+# 1ca54c3 (tools/diag/build_variant.sh ls "-DDPZ_WALK4_LOCKSTEP=1" 1ca54c3, ...).
 # The lone walk fold's start-up switches (DPZ_WALK4_LOCKSTEP / DPZ_WALK4_L_FIRST / DPZ_WALK_GUESS,
 # build_variant.sh libraries base / ls / lf / lslf / guess): the fold parity tests on the guess
 # library, then the bench's product-path stage (64 MiB, 1 and 3 payloads), alternating on one box.

@@ -2,6 +2,9 @@
 # The merge fold with kept payload windows (round 6) against the committed build (lib_base) and
 # against itself with DPZ_MERGE_KEEP=0, alternating on one box (tools/diag/merge_time.py cases),
 # after the merge fold's parity tests on the working tree's product library.
+# The same loop measured two hit chains per lane (lib_keep built with -DDPZ_MERGE_HIT2=1,
+# profiles/r06_merge_hit2_ab.jsonl); that switch was removed after its A/B: build lib_keep from
+# commit 1ca54c3 (tools/diag/build_variant.sh keep "-DDPZ_MERGE_HIT2=1" 1ca54c3) to re-run it.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}"
 mkdir -p gpurun_out
 timeout -k 10 400 python -u -m pytest tests/test_gpu_fold_merge.py tests/test_gpu_codec.py tests/test_gpu_fullsize.py -m gpu -x -q --timeout 120 --timeout-method thread -p no:cacheprovider > gpurun_out/keep_tests.log 2>&1 || { echo "tests failed"; tail -30 gpurun_out/keep_tests.log; exit 1; }
