@@ -248,6 +248,14 @@ SIGNATURES = {
                                       _c_void_p]),
     "dpz_choco_fold_nodes": (_int, [_int, _c_void_p, _c_void_p, _i64, _i64, ctypes.c_float,
                                     _c_void_p, _i64, _c_void_p]),
+    "dpz_quant_row_words": (_i64, [_i64, _int]),
+    "dpz_quant_encode_nodes_workspace_bytes": (_size, [_int, _i64]),
+    "dpz_quant_encode_nodes": (_int, [_int, _c_void_p, _i64, _i64, _int, _c_void_p, _size,
+                                      _c_void_p]),
+    "dpz_qdense_tile_elems": (_i64, [_int]),
+    "dpz_qdense_auto_mode": (_int, [_int, _i64, _i64]),
+    "dpz_qdense_average_nodes": (_int, [_int, _c_void_p, _c_void_p, _i64, _int, _i64, _i64, _int,
+                                        _c_void_p, _i64, _c_void_p]),
 }
 
 _lib = None

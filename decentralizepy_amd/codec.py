@@ -29,7 +29,9 @@ __all__ = ["DPZ_ACC_NONE", "DPZ_ACC_ACCUMULATE", "DPZ_ACC_ADD", "DPZ_EW_SUB", "D
            "mask_decode_average_nodes", "quant_encode", "quant_decode",
            "quant_block_elems", "QuantInfo", "dense_tile_elems", "dense_auto_mode", "DenseTable",
            "dense_average_nodes", "choco_chunk_elems", "choco_tile_elems", "choco_node_table",
-           "choco_encode_nodes", "ChocoTable", "choco_fold_nodes"]
+           "choco_encode_nodes", "ChocoTable", "choco_fold_nodes", "quant_row_words",
+           "quant_node_table", "quant_encode_nodes", "qdense_tile_elems", "qdense_auto_mode",
+           "QDenseTable", "qdense_average_nodes"]
 
 
 def _ptr(t):
@@ -1628,6 +1630,100 @@ def quant_decode(body, n, w, scale, out=None):
         raise ValueError("malformed quantised stream")
     check(rc, "dpz_quant_decode")
     return out[:n]
+
+
+QROW_INFO = 4   # int32 words of a packed quantised row in front of its info record
+QROW_BODY = 12  # ... and in front of its body
+
+
+def quant_row_words(n, slot_bits):
+    """int32 words of a packed quantised row ``[count (int64), status, 0 | 8 info words | body]``
+    whose body holds n fields of ``slot_bits`` bits."""
+    words = int(_lib.lib().dpz_quant_row_words(int(n), int(slot_bits)))
+    if not words:
+        raise ValueError("n must lie in [1, 2^31) and slot_bits in [2, 32]")
+    return words
+
+
+def quant_node_table(x, rows):
+    """The DEVICE node table of ``quant_encode_nodes``: 2 64-bit words per node {x, packed row}.
+    Each argument is a 2-D tensor (one row per node) or a list of per-node tensors."""
+    dev = (x if isinstance(x, torch.Tensor) else x[0]).device
+    return _ptr_table((x, rows), len(x), dev)
+
+
+def quant_encode_nodes(table, n, k, slot_bits, workspace=None):
+    """``quant_encode`` of every node of ``table`` (``quant_node_table``) with float_precision k
+    in two launches whatever the node count, each into its packed row: the info record and the
+    body bit for bit the single call's, the row's status word = the info record's (1 all zero, 2
+    non-finite, 3 underflow, 4 a field wider than ``slot_bits``; the body of such a row is not
+    written).  Nothing is read back.  ``workspace``: a uint8 device tensor kept by the caller
+    (allocated here when None); returned."""
+    _require(table, torch.int64, "table")
+    m = table.shape[0]
+    need = int(_lib.lib().dpz_quant_encode_nodes_workspace_bytes(m, int(n)))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=table.device)
+    rc = _lib.lib().dpz_quant_encode_nodes(m, _ptr(table), int(n), int(k), int(slot_bits),
+                                           _ptr(workspace), workspace.numel(),
+                                           _stream(table.device))
+    check(rc, "dpz_quant_encode_nodes")
+    return workspace
+
+
+def qdense_tile_elems(n_src):
+    """The column tile of the staged quantised fold for ``n_src`` packed rows (0: direct only)."""
+    return int(_lib.lib().dpz_qdense_tile_elems(int(n_src)))
+
+
+def qdense_auto_mode(n_src, row_reads, n):
+    """The path DPZ_DENSE_AUTO takes in ``qdense_average_nodes``."""
+    return int(_lib.lib().dpz_qdense_auto_mode(int(n_src), int(row_reads), int(n)))
+
+
+class QDenseTable(_WordTable):
+    """The fold table of ``qdense_average_nodes`` (a ``_WordTable``), with the counts the call
+    repeats."""
+
+    def __init__(self, srcs, recvs, device):
+        """srcs: the packed rows (a 2-D int32 tensor or a list of 1-D tensors); recvs: per
+        receiver ``(out row, own fp32 row, w_self, [(source index, weight), ...])`` in fold
+        order.  Weights are Python floats, rounded to fp32 here as torch rounds a scalar."""
+        src_ptrs = _row_ptrs(srcs, srcs.shape[0] if isinstance(srcs, torch.Tensor) else len(srcs))
+        self.n_src, self.m = len(src_ptrs), len(recvs)
+        self.n_entries = sum(len(r[3]) for r in recvs)
+        words, halves = self._words(self.n_src + 4 * self.m + self.n_entries)
+        words[:self.n_src] = src_ptrs
+        ent = self.n_src + 4 * self.m
+        start = 0
+        for j, (out, own, w_self, pairs) in enumerate(recvs):
+            b = self.n_src + 4 * j
+            words[b], words[b + 1] = out.data_ptr(), own.data_ptr()
+            halves[2 * b + 4] = _f32_bits(w_self)
+            halves[2 * b + 6:2 * b + 8] = (start, len(pairs))
+            for src, w in pairs:
+                halves[2 * (ent + start):2 * (ent + start) + 2] = (_i32_bits(src), _f32_bits(w))
+                start += 1
+        self._upload(device)
+
+
+def qdense_average_nodes(table, n, cap_dwords, mode=_lib.DPZ_DENSE_AUTO, guard=None,
+                         check_rc=True):
+    """Every receiver's fold of ``table`` (a ``QDenseTable``) in one launch: the dense fold of
+    ``dense_average_nodes`` over sources that are packed quantised rows, each decoded with the
+    width and scale of its own header as ``quant_decode`` decodes it; every row holds
+    ``cap_dwords`` body dwords.  ``guard`` (int32 device words, e.g. the rows' status words): if
+    any is nonzero every out row becomes a bitwise copy of its own row.  Returns the library's
+    code (raises unless it is DPZ_OK when ``check_rc``)."""
+    _require(table.dev, torch.int64, "table")
+    _require(guard, torch.int32, "guard")
+    rc = _lib.lib().dpz_qdense_average_nodes(
+        table.m, _ptr(table.dev), ctypes.c_void_p(table.host.ctypes.data), table.n_entries,
+        table.n_src, int(n), int(cap_dwords), int(mode), _ptr(guard),
+        guard.numel() if guard is not None else 0, _stream(table.dev.device))
+    if check_rc:
+        check(rc, "dpz_qdense_average_nodes")
+    return rc
 
 
 class KernelTimer:

@@ -903,6 +903,60 @@ int dpz_choco_fold_nodes(int m, const void* fold_table, const void* host_table, 
                          int64_t n, float step_size, const int32_t* guard, int64_t guard_n,
                          dpz_stream_t stream);
 
+/* ---- Quantised full-model rounds of a rank's nodes at once (decentralizepy_amd/gossip_quant.py) -
+ * Reference sharing/Sharing.py and sharing/PlainAverageSharing.py with compress = True and
+ * compression_class = Quantization: every sender's model travels as its quantised stream and a
+ * receiver folds the decoded streams with its own fp32 model.  A node's packed row is 4-byte
+ * aligned int32 words
+ *   [count = n (int64 as two words), status, 0 | the 8 info words of dpz_quant_encode | body],
+ * dpz_quant_row_words(n, slot_bits) = 12 + ceil(n * slot_bits / 32) words (0 for n < 1,
+ * n >= 2^31 or slot_bits outside [2, 32]); the status word repeats info[0].
+ * dpz_quant_encode_nodes: dpz_quant_encode of m vectors of one length n in TWO launches whatever
+ * m is, the node in the grid's second dimension.  node_table is a DEVICE array of m entries of 2
+ * 64-bit words {x, packed row}.  Per node the info words and the body are bit for bit what
+ * dpz_quant_encode(x, n, k, body, 4 * ceil(n * slot_bits / 32), info, ...) writes, statuses 1-4
+ * included: nothing is written to the body of a row whose status is nonzero, and a field wider
+ * than slot_bits is status 4, never a write past the slot.  x is read with 16-byte loads where it
+ * is 16-byte aligned, per element otherwise (chosen per node on the device); a row needs 4-byte
+ * alignment only.  Nothing is read back, nothing synchronises.  ws:
+ * dpz_quant_encode_nodes_workspace_bytes(m, n) DEVICE bytes, 16-byte aligned (each node has its
+ * own 256 max words and chunk sums).  All checks come before anything is enqueued: DPZ_ERR_ARG
+ * for m < 1, n < 1, k outside [1, 2^30], slot_bits outside [2, 32], null or misaligned pointers;
+ * DPZ_ERR_UNSUPPORTED for n >= 2^31 or m > 65535; DPZ_ERR_WORKSPACE for a short workspace.
+ * dpz_qdense_average_nodes: dpz_dense_average_nodes with packed rows as the sources.  fold_table
+ * is a DEVICE array of 64-bit words: n_src packed-row pointers, then m receivers of 4 words {out,
+ * own (the receiver's fp32 model, n elements), w_self (fp32) in the low half, start (int32) |
+ * count (int32) in the high half}, then n_entries list entries {src (int32) | w (fp32) in the
+ * high half}; host_table is the HOST copy on which every check is made before anything is
+ * enqueued.  A source's width w and scale are read from its row's header on the device (w clamped
+ * to [2, 32]; different sources may differ); its value i is
+ *   v = float(double(u - 2^(w-1) + 1) * double(scale)),
+ * u the MSB-first w-bit field at stream bits [i w, (i+1) w), as dpz_quant_decode gives it (for
+ * w <= 25 the fp32 product float(q) * scale: q is exact and the product has at most 48
+ * significant bits, so both round the same exact value once; above, the fp64 product).  No read
+ * goes past min(ceil(n w / 32), cap_dwords) dwords of a body; cap_dwords is what every source row
+ * holds.  The fold order and the empty list are those of dpz_dense_average_nodes, fp32 denormals
+ * kept.  The launch first reads guard[0, guard_n) (DEVICE int32, may be NULL with guard_n = 0,
+ * e.g. the gathered rows' status words): if any word is nonzero EVERY out row becomes a bitwise
+ * copy of its own row.  mode: DPZ_DENSE_AUTO / _STAGED / _DIRECT; the staged path decodes a column
+ * tile of dpz_qdense_tile_elems(n_src) elements (dpz_dense_tile_elems' rule, a multiple of 32: a
+ * tile starts on a dword of every body) of every source into LDS once; auto takes
+ * dpz_qdense_auto_mode(n_src, sum(count_j + 1), n).  Rows out / own that are all 16-byte aligned
+ * take 16-byte loads and stores.  DPZ_ERR_ARG: null or misaligned (4-byte) pointers, m < 1, n < 1,
+ * n_src < 1, cap_dwords < 1 or > n, a mode outside 0 .. 2, guard_n < 0 or guard words without a
+ * guard, an index outside [0, n_src), a list outside [0, n_entries), an out row that overlaps a
+ * packed row, any receiver's own row or another out row.  DPZ_ERR_UNSUPPORTED: n >= 2^31,
+ * m > 65535, the staged mode where no tile fits.                                                */
+int64_t dpz_quant_row_words(int64_t n, int slot_bits);
+size_t dpz_quant_encode_nodes_workspace_bytes(int m, int64_t n);
+int dpz_quant_encode_nodes(int m, const void* node_table, int64_t n, int64_t k, int slot_bits,
+                           void* ws, size_t ws_bytes, dpz_stream_t stream);
+int64_t dpz_qdense_tile_elems(int n_src);
+int dpz_qdense_auto_mode(int n_src, int64_t row_reads, int64_t n);
+int dpz_qdense_average_nodes(int m, const void* fold_table, const void* host_table,
+                             int64_t n_entries, int n_src, int64_t n, int64_t cap_dwords, int mode,
+                             const int32_t* guard, int64_t guard_n, dpz_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
