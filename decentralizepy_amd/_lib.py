@@ -256,6 +256,12 @@ SIGNATURES = {
     "dpz_qdense_auto_mode": (_int, [_int, _i64, _i64]),
     "dpz_qdense_average_nodes": (_int, [_int, _c_void_p, _c_void_p, _i64, _int, _i64, _i64, _int,
                                         _c_void_p, _i64, _c_void_p]),
+    "dpz_stc_chunk_elems": (_i64, []),
+    "dpz_stc_tile_elems": (_i64, []),
+    "dpz_stc_encode_workspace_bytes": (_size, [_int, _i64]),
+    "dpz_stc_encode_nodes": (_int, [_int, _c_void_p, _i64, _i64, _c_void_p, _size, _c_void_p]),
+    "dpz_stc_server_fold": (_int, [_int, _c_void_p, _c_void_p, _i64, _i64, _c_void_p, _c_void_p]),
+    "dpz_stc_apply_nodes": (_int, [_int, _c_void_p, _i64, _i64, _c_void_p, _c_void_p]),
 }
 
 _lib = None

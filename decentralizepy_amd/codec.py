@@ -31,7 +31,9 @@ __all__ = ["DPZ_ACC_NONE", "DPZ_ACC_ACCUMULATE", "DPZ_ACC_ADD", "DPZ_EW_SUB", "D
            "dense_average_nodes", "choco_chunk_elems", "choco_tile_elems", "choco_node_table",
            "choco_encode_nodes", "ChocoTable", "choco_fold_nodes", "quant_row_words",
            "quant_node_table", "quant_encode_nodes", "qdense_tile_elems", "qdense_auto_mode",
-           "QDenseTable", "qdense_average_nodes"]
+           "QDenseTable", "qdense_average_nodes", "stc_chunk_elems", "stc_tile_elems",
+           "stc_row_words", "stc_node_table", "stc_encode_nodes", "StcFoldTable",
+           "stc_server_fold", "stc_apply_table", "stc_apply_nodes"]
 
 
 def _ptr(t):
@@ -1539,6 +1541,103 @@ def choco_fold_nodes(table, n, step_size, guard=None, check_rc=True):
     if check_rc:
         check(rc, "dpz_choco_fold_nodes")
     return rc
+
+
+def stc_chunk_elems():
+    """Elements one block of ``stc_encode_nodes``' count and compaction passes covers."""
+    return int(_lib.lib().dpz_stc_chunk_elems())
+
+
+def stc_tile_elems():
+    """Elements of the server's residual a block of ``stc_server_fold`` owns."""
+    return int(_lib.lib().dpz_stc_tile_elems())
+
+
+def stc_row_words(k):
+    """int32 words of an STC packed row ``[count = k (int64), 0, 0 | up4(k) idx | up4(k) vals]``."""
+    return 4 + 2 * (-(-int(k) // 4) * 4)
+
+
+def stc_node_table(x, prev, r, rows):
+    """The DEVICE node table of ``stc_encode_nodes``: 4 64-bit words per node {x, prev, r, packed
+    row}.  Each argument is a 2-D tensor (one row per node) or a list of per-node tensors.  ``x``
+    and ``prev`` None, or None for a node in their lists: the server form (``r`` already holds
+    the change vector)."""
+    dev = (r if isinstance(r, torch.Tensor) else r[0]).device
+    m = len(r)
+
+    def ptrs(col):
+        if col is None or isinstance(col, torch.Tensor):
+            return _row_ptrs(col, m)
+        return [0 if t is None else t.data_ptr() for t in col]
+
+    tab = np.array([ptrs(c) for c in (x, prev, r, rows)], dtype=np.uint64).T.copy()
+    return torch.from_numpy(tab.view(np.int64)).to(dev)
+
+
+def stc_encode_nodes(table, n, k, workspace=None):
+    """STC's ``get_data_to_send`` of every node of ``table`` (``stc_node_table``): per node
+    ``c = (x - prev) + r``, the exact top-k of ``|c|`` (ties to the lowest indices) into its packed
+    row, ``prev = x`` and ``r = c`` with +0 at the sent entries; a node in server form selects from
+    ``r`` as it is.  One launch set for all nodes, nothing read back.  ``workspace``: a uint8
+    device tensor kept by the caller (allocated here when None); returned."""
+    _require(table, torch.int64, "table")
+    m = table.shape[0]
+    need = int(_lib.lib().dpz_stc_encode_workspace_bytes(m, int(n)))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=table.device)
+    rc = _lib.lib().dpz_stc_encode_nodes(m, _ptr(table), int(n), int(k), _ptr(workspace),
+                                         workspace.numel(), _stream(table.device))
+    check(rc, "dpz_stc_encode_nodes")
+    return workspace
+
+
+class StcFoldTable(_WordTable):
+    """The table of ``stc_server_fold`` (a ``_WordTable``): 2 words per payload {packed row,
+    weight}, in fold order."""
+
+    def __init__(self, pays, device):
+        """pays: ``[(packed row, weight), ...]`` in fold order.  Rows are tensors or device
+        addresses; weights are Python floats, rounded to fp32 here as torch rounds a scalar."""
+        self.n_payloads = len(pays)
+        words, halves = self._words(2 * self.n_payloads)
+        for p, (row, w) in enumerate(pays):
+            words[2 * p] = row.data_ptr() if isinstance(row, torch.Tensor) else int(row)
+            halves[4 * p + 2] = _f32_bits(w)
+        self._upload(device)
+
+
+def stc_server_fold(table, n, k, r_s, check_rc=True):
+    """STC's ``_averaging_server`` over the payloads of ``table`` (a ``StcFoldTable``) in one
+    launch, in place: ``total = 0; total[idx_p] += vals_p w_p`` in table order, then
+    ``r_s += total``, each operation rounded to fp32 on its own.  Returns the library's code
+    (raises unless it is DPZ_OK when ``check_rc``)."""
+    _require(table.dev, torch.int64, "table")
+    _require(r_s, torch.float32, "r_s")
+    rc = _lib.lib().dpz_stc_server_fold(
+        table.n_payloads, _ptr(table.dev), ctypes.c_void_p(table.host.ctypes.data), int(n),
+        int(k), _ptr(r_s), _stream(table.dev.device))
+    if check_rc:
+        check(rc, "dpz_stc_server_fold")
+    return rc
+
+
+def stc_apply_table(xs):
+    """The DEVICE table of ``stc_apply_nodes``: one row pointer per target model (a 2-D tensor or
+    a list of per-model tensors)."""
+    dev = (xs if isinstance(xs, torch.Tensor) else xs[0]).device
+    return _ptr_table((xs,), len(xs), dev).reshape(-1)
+
+
+def stc_apply_nodes(table, n, k, row):
+    """STC's ``process_received`` of every model of ``table`` (``stc_apply_table``) in one launch,
+    in place: ``x[idx] += vals`` over the packed broadcast ``row``; the elements the row does not
+    name keep their bits."""
+    _require(table, torch.int64, "table")
+    _require(row, torch.int32, "row")
+    rc = _lib.lib().dpz_stc_apply_nodes(table.numel(), _ptr(table), int(n), int(k), _ptr(row),
+                                        _stream(table.device))
+    check(rc, "dpz_stc_apply_nodes")
 
 
 class QuantInfo:

@@ -957,6 +957,55 @@ int dpz_qdense_average_nodes(int m, const void* fold_table, const void* host_tab
                              int64_t n_entries, int n_src, int64_t n, int64_t cap_dwords, int mode,
                              const int32_t* guard, int64_t guard_n, dpz_stream_t stream);
 
+/* ---- An STC round of a federation at once (decentralizepy_amd/gossip_stc.py) --------------------
+ * Reference sharing/STC.py: sparse top-k with residual error feedback, clients and a server that
+ * compresses its broadcast with a residual of its own.  Finite inputs only.  A packed row is
+ * [count = k (int64 as two words), status = 0, 0 | up4(k) x int32 idx | up4(k) x fp32 val], 4-byte
+ * aligned, up4(k) = k rounded up to a multiple of 4; exactly k entries are written, the words past
+ * them and past the row are untouched.
+ * dpz_stc_encode_nodes: the exact-k selection of m nodes of one size n.  node_table is a DEVICE
+ * array of m entries of 4 64-bit words {x, prev, r, row}.  Per node, with one fp32 rounding per
+ * operation, c_i = fl(fl(x_i - prev_i) + r_i); the k largest keys |c_i| (NaN ranks above +inf) are
+ * selected, ties at the k-th key going to the lowest indices; idx = the selection ascending,
+ * val = c[idx]; afterwards prev = x, r_i = +0 where selected and c_i elsewhere: bit for bit
+ * dpz_topk_encode(x, prev, r, DPZ_ACC_ACCUMULATE, vals_src = r, DPZ_TOPK_EXACT) and a copy of x to
+ * prev.  An entry with x == NULL is in server form: r already holds c, nothing is formed and prev
+ * is not touched.  The first histogram pass forms c and stores it into r and x into prev; every
+ * later pass reads r alone.  16-byte loads and stores where the node's rows are 16-byte aligned,
+ * per element otherwise (chosen per node on the device).  One memset and nine launches whatever m
+ * is: three histogram passes, each with a 1-block-per-node resolve, a count pass over chunks of
+ * dpz_stc_chunk_elems() elements (key > T and key == T), a 1-block-per-node scan that allots the
+ * ties in index order, and the ordered compaction.  No float atomics; the result does not depend
+ * on the grid; no host synchronisation.  ws: dpz_stc_encode_workspace_bytes(m, n) DEVICE bytes,
+ * 4-byte aligned, any content.  All checks come before anything is enqueued: DPZ_ERR_ARG for
+ * m < 1, n < 1, k < 1, k > n, null or misaligned pointers; DPZ_ERR_UNSUPPORTED for n >= 2^31 or
+ * m > 65535; DPZ_ERR_WORKSPACE for a short workspace.
+ * dpz_stc_server_fold: `_averaging_server` in ONE launch, in place on r_s (fp32, n elements).
+ * table is a DEVICE array of n_payloads entries of 2 64-bit words {packed row, w (fp32) in the low
+ * half}; host_table is the HOST copy on which every check is made.  total starts at +0; for each
+ * payload in table order total[idx[e]] = fl(total[idx[e]] + fl(val[e] w)); then
+ * r_s = fl(r_s + total).  A block owns a tile of dpz_stc_tile_elems() elements and keeps its total
+ * in LDS; there is no n-length temporary.  A row's count is read from its header (clamped to k);
+ * indices are ascending and unique within a row; an index outside the tile or outside [0, n) is
+ * skipped, never written through.  DPZ_ERR_ARG: n_payloads < 1, n < 1, k < 1, k > n, null or
+ * misaligned pointers, a non-finite weight, a payload row that overlaps r_s.
+ * DPZ_ERR_UNSUPPORTED: n >= 2^31.
+ * dpz_stc_apply_nodes: `process_received` of m models in ONE launch, in place.  table is a DEVICE
+ * array of m fp32 row pointers (n elements each, distinct rows); for each of them
+ * x[idx[e]] = fl(x[idx[e]] + val[e]) over the entries of the packed row `row`.  Indices are unique:
+ * no atomics.  An index outside [0, n) is skipped; an element the row does not name keeps its bits
+ * (a -0 too, where the reference's dense add gives +0).  DPZ_ERR_ARG: m < 1, n < 1, k < 1, k > n,
+ * null or misaligned pointers.  DPZ_ERR_UNSUPPORTED: n >= 2^31 or m > 65535.                   */
+int64_t dpz_stc_chunk_elems(void);
+int64_t dpz_stc_tile_elems(void);
+size_t dpz_stc_encode_workspace_bytes(int m, int64_t n);
+int dpz_stc_encode_nodes(int m, const void* node_table, int64_t n, int64_t k, void* ws,
+                         size_t ws_bytes, dpz_stream_t stream);
+int dpz_stc_server_fold(int n_payloads, const void* table, const void* host_table, int64_t n,
+                        int64_t k, float* r_s, dpz_stream_t stream);
+int dpz_stc_apply_nodes(int m, const void* table, int64_t n, int64_t k, const int32_t* row,
+                        dpz_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
