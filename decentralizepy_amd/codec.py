@@ -33,7 +33,9 @@ __all__ = ["DPZ_ACC_NONE", "DPZ_ACC_ACCUMULATE", "DPZ_ACC_ADD", "DPZ_EW_SUB", "D
            "quant_node_table", "quant_encode_nodes", "qdense_tile_elems", "qdense_auto_mode",
            "QDenseTable", "qdense_average_nodes", "stc_chunk_elems", "stc_tile_elems",
            "stc_row_words", "stc_node_table", "stc_encode_nodes", "StcFoldTable",
-           "stc_server_fold", "stc_apply_table", "stc_apply_nodes"]
+           "stc_server_fold", "stc_apply_table", "stc_apply_nodes", "topkacc_chunk_elems",
+           "topkacc_row_words", "topkacc_node_table", "topkacc_encode_nodes",
+           "topkacc_post_nodes"]
 
 
 def _ptr(t):
@@ -1638,6 +1640,56 @@ def stc_apply_nodes(table, n, k, row):
     rc = _lib.lib().dpz_stc_apply_nodes(table.numel(), _ptr(table), int(n), int(k), _ptr(row),
                                         _stream(table.device))
     check(rc, "dpz_stc_apply_nodes")
+
+
+def topkacc_chunk_elems():
+    """Elements one block of ``topkacc_encode_nodes``' count and compaction passes covers."""
+    return int(_lib.lib().dpz_topkacc_chunk_elems())
+
+
+def topkacc_row_words(k):
+    """int32 words of a packed row ``[count = k (int64), 0, 0 | up4(k) idx | up4(k) vals]``."""
+    return 4 + 2 * (-(-int(k) // 4) * 4)
+
+
+def topkacc_node_table(x, x0, acc, rows, key=None, counter=None):
+    """The DEVICE node table of ``topkacc_encode_nodes`` and ``topkacc_post_nodes``: 6 64-bit
+    words per node {x, x0, acc, key, counter or 0, packed row}.  Each argument is a 2-D tensor (one
+    row per node) or a list of per-node tensors.  ``key``: the scratch rows of DPZ_ACC_ADD (not
+    read with DPZ_ACC_ACCUMULATE, whose key row is ``acc``); ``rows`` may be None for a table that
+    only ``topkacc_post_nodes`` reads."""
+    dev = (x if isinstance(x, torch.Tensor) else x[0]).device
+    return _ptr_table((x, x0, acc, key, counter, rows), len(x), dev)
+
+
+def topkacc_encode_nodes(table, n, k, mode, workspace=None):
+    """PartialModel's ``_pre_step`` + ``serialized_model`` with accumulation of every node of
+    ``table`` (``topkacc_node_table``).  mode DPZ_ACC_ACCUMULATE: ``acc += x - x0`` everywhere, the
+    key is ``|acc|``; DPZ_ACC_ADD: the key is ``|(x - x0) + acc|``, formed into the table's key
+    rows, ``acc`` unchanged before the rewind.  Per node the exact top-k of the key (ties to the
+    lowest indices) into its packed row with ``vals = x[idx]``, ``counter[idx] += 1`` and
+    ``acc[idx] = +0``.  One launch set for all nodes, nothing read back.  ``workspace``: a uint8
+    device tensor kept by the caller (allocated here when None); returned."""
+    _require(table, torch.int64, "table")
+    m = table.shape[0]
+    need = int(_lib.lib().dpz_topkacc_encode_workspace_bytes(m, int(n)))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=table.device)
+    rc = _lib.lib().dpz_topkacc_encode_nodes(m, _ptr(table), int(n), int(k), int(mode),
+                                             _ptr(workspace), workspace.numel(),
+                                             _stream(table.device))
+    check(rc, "dpz_topkacc_encode_nodes")
+    return workspace
+
+
+def topkacc_post_nodes(table, n):
+    """PartialModel's accumulating ``_post_step`` of every node of ``table``
+    (``topkacc_node_table``) in one launch: ``acc += x - x0``, x the averaged model and x0 the model
+    the round started from."""
+    _require(table, torch.int64, "table")
+    rc = _lib.lib().dpz_topkacc_post_nodes(table.shape[0], _ptr(table), int(n),
+                                           _stream(table.device))
+    check(rc, "dpz_topkacc_post_nodes")
 
 
 class QuantInfo:

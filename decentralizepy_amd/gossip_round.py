@@ -1,7 +1,7 @@
 """What the whole-topology round engines (gossip.py, gossip_jwins.py, gossip_subsampling.py,
-gossip_epidemic.py, gossip_choco.py, gossip_quant.py, gossip_stc.py) share: ``ShardedRound``, the
-sharding of the nodes over the ranks, and ``PackedRowRound``, the packed row per node that one
-all-gather exchanges."""
+gossip_epidemic.py, gossip_choco.py, gossip_quant.py, gossip_stc.py, gossip_topkacc.py) share:
+``ShardedRound``, the sharding of the nodes over the ranks, and ``PackedRowRound``, the packed row
+per node that one all-gather exchanges."""
 import math
 
 import numpy as np

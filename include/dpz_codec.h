@@ -1006,6 +1006,46 @@ int dpz_stc_server_fold(int n_payloads, const void* table, const void* host_tabl
 int dpz_stc_apply_nodes(int m, const void* table, int64_t n, int64_t k, const int32_t* row,
                         dpz_stream_t stream);
 
+/* ---- A top-k round with accumulated changes at once (decentralizepy_amd/gossip_topkacc.py) ------
+ * Reference sharing/PartialModel.py with accumulation = True, both settings of
+ * accumulate_averaging_changes (:305-331 `_pre_step`, :188-255 the selection, the counter and the
+ * rewind, :333-353 `_post_step`).  Finite inputs only.  The packed row is STC's:
+ * [count = k (int64 as two words), status = 0, 0 | up4(k) x int32 idx | up4(k) x fp32 val], 4-byte
+ * aligned; exactly k entries are written, the words past them and past the row are untouched.
+ * dpz_topkacc_encode_nodes: the exact-k selection of m nodes of one size n.  node_table is a DEVICE
+ * array of m entries of 6 64-bit words {x, x0, acc, key, counter (or 0), row}.  Per node, with one
+ * fp32 rounding per operation:
+ *   mode DPZ_ACC_ACCUMULATE  acc_i = fl(acc_i + fl(x_i - x0_i)) everywhere, the key is |acc_i|; the
+ *                            key row is acc itself (the entry's key word is not read);
+ *   mode DPZ_ACC_ADD         the key is |fl(fl(x_i - x0_i) + acc_i)|, formed once into the scratch
+ *                            row `key` (n floats, any content, overwritten); acc is not written
+ *                            before the rewind.
+ * The k largest keys (NaN ranks above +inf) are selected, ties at the k-th key going to the lowest
+ * indices; idx = the selection ascending, val = x[idx]; counter[idx] += 1 (plain stores: an element
+ * has one owner); acc[idx] = +0: bit for bit dpz_topk_encode(x, x0, acc, mode, vals_src = x, ...,
+ * counter, DPZ_TOPK_EXACT) per node.  x and x0 are never written.  The first histogram pass reads
+ * x, x0 and acc and stores the key row; every later pass reads the key row alone.  16-byte loads and
+ * stores where the node's rows are 16-byte aligned, per element otherwise (chosen per node on the
+ * device).  One memset and nine launches whatever m is: three histogram passes (10/11/10 bits),
+ * each with a 1-block-per-node resolve, a count pass over chunks of dpz_topkacc_chunk_elems()
+ * elements, a 1-block-per-node scan that allots the ties in index order, and the ordered
+ * compaction.  No float atomics; the result does not depend on the grid; no host synchronisation.
+ * ws: dpz_topkacc_encode_workspace_bytes(m, n) DEVICE bytes, 4-byte aligned, any content.  All
+ * checks come before anything is enqueued: DPZ_ERR_ARG for m < 1, a null or misaligned table or
+ * workspace, n outside [1, 2^31), k outside [1, n], a mode other than the two above, a short
+ * workspace; DPZ_ERR_UNSUPPORTED for m > 65535.
+ * dpz_topkacc_post_nodes: the accumulating `_post_step` (accumulate_averaging_changes = True) of m
+ * nodes in ONE launch over the same node table, of which it reads {x, x0, acc}:
+ * acc_i = fl(acc_i + fl(x_i - x0_i)), x the averaged model and x0 the model the round started
+ * from; x and x0 are not written.  16-byte accesses where a node's three rows are aligned.
+ * DPZ_ERR_ARG: m < 1, a null or misaligned table, n outside [1, 2^31); DPZ_ERR_UNSUPPORTED:
+ * m > 65535.                                                                                   */
+int64_t dpz_topkacc_chunk_elems(void);
+size_t dpz_topkacc_encode_workspace_bytes(int m, int64_t n);
+int dpz_topkacc_encode_nodes(int m, const void* node_table, int64_t n, int64_t k, int mode,
+                             void* ws, size_t ws_bytes, dpz_stream_t stream);
+int dpz_topkacc_post_nodes(int m, const void* node_table, int64_t n, dpz_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
