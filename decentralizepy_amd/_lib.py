@@ -198,6 +198,7 @@ SIGNATURES = {
                                _c_void_p, _int, _c_void_p, _c_void_p, _size, _c_void_p]),
     "dpz_idwt_generic": (_int, [_c_void_p, _i64, _int, _c_void_p, _int, _c_void_p, _c_void_p,
                                 _size, _c_void_p]),
+    "dpz_lz4_geometry": (_int, [ctypes.POINTER(ctypes.c_int32)]),
     "dpz_lz4_max_bytes": (_i64, [_i64]),
     "dpz_lz4_workspace_bytes": (_size, [_i64, _i64, _i64]),
     "dpz_lz4_compress": (_int, [_c_void_p, _i64, _c_void_p, _i64, ctypes.POINTER(_i64),

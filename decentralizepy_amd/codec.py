@@ -21,7 +21,7 @@ __all__ = ["DPZ_ACC_NONE", "DPZ_ACC_ACCUMULATE", "DPZ_ACC_ADD", "DPZ_EW_SUB", "D
            "topk_complete", "decode_average", "replace", "wavedec_len", "wavedec", "waverec",
            "pack_fp16", "unpack_fp16", "elias_encode", "elias_decode", "elias_decode_async",
            "KernelTimer", "NodeStepBatch", "topk_sticky_status", "rfft", "irfft", "fft_native", "cplx_key",
-           "cplx_gather", "cplx_pair_indices", "lz4_compress", "lz4_decompress", "lz4_frame_info",
+           "cplx_gather", "cplx_pair_indices", "lz4_compress", "lz4_decompress", "lz4_frame_info", "lz4_geometry",
            "delta_i32", "running_sum_i32", "mask_words", "topk_encode_sliced", "counter_unslice",
            "counter_slice", "rewind_apply", "counter_flush", "counter_flush_batch", "mt_mask",
            "mt_rank_entries", "mask_gather", "mask_decode_average", "mt_mask_batch",
@@ -1059,8 +1059,9 @@ def _lz4_ws(workspace, device, need):
 
 
 def lz4_compress(data, out=None, workspace=None):
-    """LZ4 frame of a device byte tensor (csrc/dpz_lz4.hip: independent 4 KB blocks, one wave
-    each); returns a device uint8 view of exactly the frame (reference Lz4Wrapper.py:20-98)."""
+    """LZ4 frame of a device byte tensor (csrc/dpz_lz4.hip: linked 2 KB blocks, one wave each,
+    whose matches reach 14 KB back into the input; ``lz4_geometry()`` has the built figures);
+    returns a device uint8 view of exactly the frame (reference Lz4Wrapper.py:20-98)."""
     _require(data, torch.uint8, "data")
     n = data.numel()
     cap = int(_lib.lib().dpz_lz4_max_bytes(n))
@@ -1072,6 +1073,15 @@ def lz4_compress(data, out=None, workspace=None):
                                      _ptr(ws), ws.numel(), _stream(data.device))
     check(rc, "dpz_lz4_compress")
     return out[:nbytes.value]
+
+
+def lz4_geometry():
+    """The built LZ4 codec's geometry (host only, no GPU): ``blk`` encoder block bytes, ``win``
+    encoder history bytes, ``par_max`` / ``par_cmax`` decoded / compressed bytes of a block the
+    parallel decoder takes, ``chunk`` its walk chunk in compressed bytes."""
+    g = (ctypes.c_int32 * 5)()
+    check(_lib.lib().dpz_lz4_geometry(g), "dpz_lz4_geometry")
+    return dict(zip(("blk", "win", "par_max", "par_cmax", "chunk"), (int(v) for v in g)))
 
 
 def lz4_frame_info(frame):
@@ -1101,6 +1111,8 @@ def lz4_decompress(frame, device, out=None, workspace=None, max_size=None):
     if cs > bound or (max_size is not None and cs > int(max_size)):
         raise ValueError(f"malformed LZ4 frame: content size {cs} exceeds what its {nb} "
                          f"blocks can hold ({bound} bytes) or max_size")
+    if bmax > 65536 and nb > 0:  # what dpz_lz4_decompress answers, before anything is allocated
+        check(_lib.DPZ_ERR_UNSUPPORTED, "dpz_lz4_decompress")
     # without a stored content size the blocks bound it
     size = cs if cs >= 0 else (min(bound, int(max_size)) if max_size is not None else bound)
     if out is None or out.numel() < size:
@@ -1135,8 +1147,8 @@ def lz4_decompress(frame, device, out=None, workspace=None, max_size=None):
 def delta_i32(idx, out=None):
     """``np.diff(idx, prepend=0).astype(np.int32)`` of a device int32 vector."""
     _require(idx, torch.int32, "idx")
-    if out is None:
-        out = torch.empty_like(idx)
+    if out is None:  # (not empty_like: an empty idx may carry a zero stride, which no view takes)
+        out = torch.empty(idx.shape, dtype=torch.int32, device=idx.device)
     rc = _lib.lib().dpz_delta_i32(_ptr(idx), idx.numel(), _ptr(out), _stream(idx.device))
     check(rc, "dpz_delta_i32")
     return out

@@ -126,7 +126,7 @@ __device__ __forceinline__ void lz_stage(uint8_t* dst, const uint8_t* __restrict
   }
 }
 
-// one wave per 4 KB block; blocks of 64 threads
+// one wave per LZ_BLK (2 KB) block of a linked frame; workgroups of 64 threads
 __global__ void __launch_bounds__(64) lz4_encode_blocks(const uint8_t* __restrict__ in, int64_t n,
                                                        uint8_t* __restrict__ slots,
                                                        uint32_t* __restrict__ bsize) {
@@ -562,7 +562,9 @@ __device__ __forceinline__ LzSeq lz_parse_at(const uint8_t* cb, uint32_t p, uint
   }
   M += 4;
   if (M > (uint32_t)LZ_PAR_MAX) { q.kind = 3; return q; }
-  if (ip > cs) return q;
+  // a sequence with a match is followed by another token (the block's last sequence is literals
+  // only): one that ends at or past the block's end is no sequence, so no chain can end on it
+  if (ip >= cs) return q;
   q.M = M;
   q.next = ip;
   q.kind = 0;
@@ -618,9 +620,10 @@ __global__ void __launch_bounds__(LZ_PAR_T) lz4_decode_par_kernel(const uint8_t*
     uint16_t nx;
     if (L == 15 || M == 15) {
       nx = LZ_SLOW;
-    } else {  // literals [p + 1, p + 1 + L), then the end of the block or a 2-byte offset
+    } else {  // literals [p + 1, p + 1 + L), then the end of the block or a 2-byte offset with
+              // a token after it (a match never ends the block: lz_parse_at)
       const uint32_t ip = p + 1 + L;
-      nx = ip > cs ? LZ_BAD : (ip == cs ? (uint16_t)cs : (ip + 2 > cs ? LZ_BAD : (uint16_t)(ip + 2)));
+      nx = ip > cs ? LZ_BAD : (ip == cs ? (uint16_t)cs : (ip + 2 >= cs ? LZ_BAD : (uint16_t)(ip + 2)));
     }
     S.nxt[p] = nx;
     S.tok[p] = 0;
@@ -1019,6 +1022,16 @@ static uint32_t xxh32_small(const uint8_t* p, int len) {
 
 using namespace dpz;
 
+extern "C" int dpz_lz4_geometry(int32_t* out5) {
+  if (!out5) return DPZ_ERR_ARG;
+  out5[0] = LZ_BLK;
+  out5[1] = LZ_WIN;
+  out5[2] = LZ_PAR_MAX;
+  out5[3] = LZ_PAR_CMAX;
+  out5[4] = LZ_PAR_CHUNK;
+  return DPZ_OK;
+}
+
 extern "C" int64_t dpz_lz4_max_bytes(int64_t n) {
   if (n < 0) return -1;
   const int64_t nblk = (n + LZ_BLK - 1) / LZ_BLK;
@@ -1106,6 +1119,7 @@ extern "C" int dpz_lz4_frame_info(const uint8_t* frame_host, int64_t nbytes, int
     if (pos > nbytes) return DPZ_ERR_ARG;
     ++nb;
   }
+  if ((flg & 0x04) && nbytes < pos + 4) return DPZ_ERR_ARG;  // the content checksum is cut off
   *content_size = cs;
   *nblk = nb;
   *linked = (flg & 0x20) ? 0 : 1;
@@ -1265,7 +1279,8 @@ extern "C" int dpz_lz4_decompress(const uint8_t* frame_dev, const uint8_t* frame
 
 extern "C" int dpz_delta_i32(const int32_t* in, int64_t k, int32_t* out, dpz_stream_t stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (k < 0 || (k > 0 && (!in || !out)) || in == out) return DPZ_ERR_ARG;
+  // (an empty vector may come with two null pointers: only a non-empty one is checked in place)
+  if (k < 0 || (k > 0 && (!in || !out || in == out))) return DPZ_ERR_ARG;
   if (k == 0) return DPZ_OK;
   int64_t g = (k + 255) / 256;
   if (g > 4096) g = 4096;

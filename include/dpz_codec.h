@@ -659,12 +659,16 @@ int dpz_cplx_gather(const float* src, int64_t m, const int32_t* idx, int64_t k, 
 int dpz_cplx_pair_indices(const int32_t* idx, int64_t k, int32_t* pair, dpz_stream_t stream);
 
 /* ---- LZ4 frames (the wire format of compression/Lz4Wrapper.py:20-98, lz4.frame) -------------
- * Encoder: independent 2 KB blocks, one wave each (B.Indep, BD = 64 KB, content size stored, no
- * checksums): a valid LZ4 frame any decoder reads; the bytes are this build's (greedy parse over a
- * 11-bit hash of 4-byte words; python-lz4's match finder is not reproduced, so byte parity is
- * unpinned).  Decoder: any LZ4 frame with 64 KB (or smaller) blocks, linked (python-lz4's
+ * Encoder: linked 2 KB blocks, one wave each, whose matches reach 14 KB back (B.Indep clear,
+ * BD = 64 KB, content size stored, no checksums): a valid LZ4 frame any decoder reads; the bytes
+ * are this build's (greedy parse over a 12-bit hash of 5 bytes; python-lz4's match finder is not
+ * reproduced, so byte parity is unpinned).  Decoder: any LZ4 frame with 64 KB blocks, linked (python-lz4's
  * default, decoded by one workgroup) or independent (one workgroup per block); content and
  * block checksums are skipped, dictionary IDs rejected.                                         */
+/* The built codec's geometry, for tests that place inputs at its edges: out5 = {encoder block
+ * bytes, encoder history bytes, decoded bytes per block on the parallel decoder, compressed bytes
+ * per block on it, its walk chunk in compressed bytes}.  Host only; DPZ_ERR_ARG on a null out5. */
+int dpz_lz4_geometry(int32_t* out5);
 /* Upper bound of the frame size for n input bytes. */
 int64_t dpz_lz4_max_bytes(int64_t n);
 /* Device workspace for an encode of n bytes (nblk = bmax = 0) or a decode of a frame of nblk
