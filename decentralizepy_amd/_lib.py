@@ -268,6 +268,11 @@ SIGNATURES = {
     "dpz_topkacc_encode_nodes": (_int, [_int, _c_void_p, _i64, _i64, _int, _c_void_p, _size,
                                         _c_void_p]),
     "dpz_topkacc_post_nodes": (_int, [_int, _c_void_p, _i64, _c_void_p]),
+    "dpz_dwt_sym2_nodes": (_int, [_int, _c_void_p, _c_void_p, _i64, _int, _int, _c_void_p]),
+    "dpz_idwt_sym2_nodes": (_int, [_int, _c_void_p, _c_void_p, _i64, _int, _c_void_p]),
+    "dpz_jwins_chunk_elems": (_i64, []),
+    "dpz_jwins_encode_workspace_bytes": (_size, [_int, _i64]),
+    "dpz_jwins_encode_nodes": (_int, [_int, _c_void_p, _i64, _c_void_p, _size, _c_void_p]),
 }
 
 _lib = None

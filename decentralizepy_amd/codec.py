@@ -35,7 +35,8 @@ __all__ = ["DPZ_ACC_NONE", "DPZ_ACC_ACCUMULATE", "DPZ_ACC_ADD", "DPZ_EW_SUB", "D
            "stc_row_words", "stc_node_table", "stc_encode_nodes", "StcFoldTable",
            "stc_server_fold", "stc_apply_table", "stc_apply_nodes", "topkacc_chunk_elems",
            "topkacc_row_words", "topkacc_node_table", "topkacc_encode_nodes",
-           "topkacc_post_nodes"]
+           "topkacc_post_nodes", "DwtNodesTable", "IdwtNodesTable", "dwt_sym2_nodes",
+           "idwt_sym2_nodes", "jwins_chunk_elems", "JwinsEncodeTable", "jwins_encode_nodes"]
 
 
 def _ptr(t):
@@ -1702,6 +1703,120 @@ def topkacc_post_nodes(table, n):
     rc = _lib.lib().dpz_topkacc_post_nodes(table.shape[0], _ptr(table), int(n),
                                            _stream(table.device))
     check(rc, "dpz_topkacc_post_nodes")
+
+
+class DwtNodesTable(_WordTable):
+    """The table of ``dwt_sym2_nodes`` (a ``_WordTable``): 4 words per node {x, x0, coeffs_x or 0,
+    coeffs_diff or 0}.  Each argument is a 2-D tensor (one row per node), a list of per-node
+    tensors, or None (a zero column)."""
+
+    def __init__(self, x, x0, coeffs_x, coeffs_diff, device):
+        self.m = m = len(x)
+        words, _ = self._words(4 * m)
+        words[:4 * m] = np.array([_row_ptrs(c, m) for c in (x, x0, coeffs_x, coeffs_diff)],
+                                 dtype=np.uint64).T.reshape(-1)
+        self._upload(device)
+
+
+class IdwtNodesTable(_WordTable):
+    """The table of ``idwt_sym2_nodes`` (a ``_WordTable``): 2 words per node {coeffs, out}."""
+
+    def __init__(self, coeffs, out, device):
+        self.m = m = len(coeffs)
+        words, _ = self._words(2 * m)
+        words[:2 * m] = np.array([_row_ptrs(c, m) for c in (coeffs, out)],
+                                 dtype=np.uint64).T.reshape(-1)
+        self._upload(device)
+
+
+def dwt_sym2_nodes(table, n, level=4, accumulate=False, check_rc=True):
+    """``wavedec`` (sym2) of every node of ``table`` (a ``DwtNodesTable``) in ONE launch: per node
+    bit for bit ``dpz_dwt_sym2(x, x0, n, level, coeffs_x, coeffs_diff, accumulate)``.  Every row is
+    16-byte aligned and every node names the same outputs.  Returns the library's code (raises
+    unless it is DPZ_OK when ``check_rc``)."""
+    _require(table.dev, torch.int64, "table")
+    rc = _lib.lib().dpz_dwt_sym2_nodes(table.m, _ptr(table.dev),
+                                       ctypes.c_void_p(table.host.ctypes.data), int(n), int(level),
+                                       1 if accumulate else 0, _stream(table.dev.device))
+    if check_rc:
+        check(rc, "dpz_dwt_sym2_nodes")
+    return rc
+
+
+def idwt_sym2_nodes(table, n, level=4, check_rc=True):
+    """``waverec`` (sym2) of every node of ``table`` (an ``IdwtNodesTable``) in ONE launch: per
+    node bit for bit ``dpz_idwt_sym2(coeffs, n, level, out)``."""
+    _require(table.dev, torch.int64, "table")
+    rc = _lib.lib().dpz_idwt_sym2_nodes(table.m, _ptr(table.dev),
+                                        ctypes.c_void_p(table.host.ctypes.data), int(n),
+                                        int(level), _stream(table.dev.device))
+    if check_rc:
+        check(rc, "dpz_idwt_sym2_nodes")
+    return rc
+
+
+def jwins_chunk_elems():
+    """Elements one block of ``jwins_encode_nodes``' count and compaction passes covers."""
+    return int(_lib.lib().dpz_jwins_chunk_elems())
+
+
+class JwinsEncodeTable:
+    """The node table of ``jwins_encode_nodes``: 8 words per node {c, acc, vals_src, counter or 0,
+    idx_out, val_out, k, 0}.  The first four columns are set once (2-D tensors with a row per
+    node, or lists of per-node tensors; ``counter`` may be None); ``set(j, k, idx_out, val_out)``
+    fills a round's words of node j on the host (addresses or tensors; 0 / None for none), and
+    ``upload()`` enqueues the copy to the DEVICE words without waiting for it: the host words go
+    through a pinned staging block of their own per upload, which the allocator hands out again
+    only after the copy has run."""
+
+    def __init__(self, c, acc, vals_src, counter, device):
+        self.m = m = len(c)
+        self.host = np.zeros((max(1, m), 8), dtype=np.uint64)
+        for col, rows in enumerate((c, acc, vals_src, counter)):
+            self.host[:m, col] = _row_ptrs(rows, m)
+        self.dev = torch.zeros(max(1, m), 8, dtype=torch.int64, device=device)
+
+    @staticmethod
+    def _addr(t):
+        if t is None:
+            return 0
+        return t.data_ptr() if isinstance(t, torch.Tensor) else int(t)
+
+    def set(self, j, k, idx_out, val_out):
+        self.host[j, 4:] = (self._addr(idx_out), self._addr(val_out), int(k), 0)
+
+    def upload(self):
+        src = torch.from_numpy(self.host.view(np.int64))
+        if self.dev.is_cuda:
+            src = src.pin_memory()
+        self.dev.copy_(src, non_blocking=True)
+        return self
+
+
+def jwins_encode_nodes(table, n, workspace=None):
+    """JWINS's ``serialized_model`` of every node of ``table`` (an uploaded ``JwinsEncodeTable``),
+    each with its own k, in one launch set.  A node with 1 <= k <= n: the key ``|c + acc|`` is
+    formed in place into its ``c`` row, the exact top-k of it (ties to the lowest indices) goes
+    to ``idx_out`` ascending with ``val_out = vals_src[idx]``, ``counter[idx] += 1``,
+    ``acc[idx] = +0``.  A node with k = 0 shares fully: ``acc = +0`` everywhere and, with a
+    ``val_out``, ``val_out[:n] = vals_src``.  Nothing is read back.  ``workspace``: a uint8 device
+    tensor kept by the caller (allocated here when None); returned."""
+    _require(table.dev, torch.int64, "table")
+    m, n = table.m, int(n)
+    ks = table.host[:m, 6]
+    if m and int(ks.max()) > n:
+        raise ValueError(f"a node's k = {int(ks.max())} exceeds n = {n}")
+    part = ks > 0
+    if (table.host[:m, :3] == 0).any() or (table.host[:m, 4:6][part] == 0).any():
+        raise ValueError("a node table with a null row: c, acc and vals_src of every node, "
+                         "idx_out and val_out of every node with k >= 1")
+    need = int(_lib.lib().dpz_jwins_encode_workspace_bytes(m, n))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=table.dev.device)
+    rc = _lib.lib().dpz_jwins_encode_nodes(m, _ptr(table.dev), n, _ptr(workspace),
+                                           workspace.numel(), _stream(table.dev.device))
+    check(rc, "dpz_jwins_encode_nodes")
+    return workspace
 
 
 class QuantInfo:

@@ -843,6 +843,91 @@ static unsigned persistent_grid(K kernel, size_t shm, int64_t ntiles) {
   return (unsigned)(ntiles < g ? (ntiles > 0 ? ntiles : 1) : g);
 }
 
+// ---- m nodes in one launch (dpz_dwt_sym2_nodes / dpz_idwt_sym2_nodes): the node in the grid's
+// second dimension, every node with the same n and level.  New kernels beside the single-node
+// ones (whose code and resource figures are untouched), built from the same device functions: the
+// forward walks the tiles of its node on the span path at every level (the same bits as the
+// level-4 interior path: conv4r and conv4v sum in the same order), the inverse is idwt_kernel
+// with the node's rows.
+struct DwtNode {  // 4 64-bit words
+  const float* x;
+  const float* x0;
+  float* cx;  // or NULL
+  float* cd;  // or NULL
+};
+static_assert(sizeof(DwtNode) == 32, "4 64-bit words");
+
+struct IdwtNode {  // 2 64-bit words
+  const float* coeffs;
+  float* out;
+};
+static_assert(sizeof(IdwtNode) == 16, "2 64-bit words");
+
+// The accumulating forms are bounded for 3 waves per SIMD: at 4 (128 VGPRs) they spill 12 to 20
+// bytes per lane to scratch, as dwt_kernel's do.
+template <bool WX, bool WD, bool ACCUM>
+__global__ void __launch_bounds__(256, ACCUM ? 3 : DPZ_DWT_WAVES) dwt_nodes_kernel(
+    const DwtNode* __restrict__ tab, Levels LV, int64_t ntiles) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const DwtNode nd = tab[blockIdx.y];
+  const int64_t n = LV.len[0];
+  int64_t tile = blockIdx.x;
+  if (tile >= ntiles) return;
+  float4 va[DWT_NG], vb[DWT_NG];
+  int64_t s0, e0;
+  dwt_span(LV, tile, &s0, &e0);
+  dwt_span_load<WD>(nd.x, nd.x0, n, s0, e0, va, vb);
+  for (;;) {
+    dwt_span_store<WX, WD>(va, vb, n, s0, e0, smem);
+    const int64_t next = tile + gridDim.x;
+    if (next < ntiles) {
+      dwt_span(LV, next, &s0, &e0);
+      dwt_span_load<WD>(nd.x, nd.x0, n, s0, e0, va, vb);
+    }
+    dwt_levels<WX, WD, ACCUM>(LV, nd.cx, nd.cd, tile, smem);
+    __syncthreads();  // the next tile reuses the LDS buffers
+    if (next >= ntiles) break;
+    tile = next;
+  }
+}
+
+template <int LEV>
+__global__ void __launch_bounds__(256) idwt_nodes_kernel(const IdwtNode* __restrict__ tab,
+                                                         Levels LV, int64_t ntiles) {
+  __shared__ __attribute__((aligned(16))) float A[IDWT_SPAN];
+  __shared__ __attribute__((aligned(16))) float B[IDWT_SPAN];
+  __shared__ __attribute__((aligned(16))) float D[idwt_doff(LEV + 1)];
+  const IdwtNode nd = tab[blockIdx.y];
+  int64_t tile = blockIdx.x;
+  if (tile >= ntiles) return;
+  float pv[idwt_npv<LEV>()];
+  IdwtRanges R = idwt_ranges<LEV>(LV, tile);
+  idwt_load<LEV>(nd.coeffs, LV, R, pv);
+  for (;;) {
+    idwt_stage<LEV>(R, pv, A, D);
+    __syncthreads();
+    const IdwtRanges Rc = R;
+    const int64_t next = tile + gridDim.x;
+    if (next < ntiles) {
+      R = idwt_ranges<LEV>(LV, next);
+      idwt_load<LEV>(nd.coeffs, LV, R, pv);
+    }
+    idwt_levels<LEV>(LV, Rc, nd.out, A, B, D);
+    __syncthreads();  // the next tile reuses A / B / D
+    if (next >= ntiles) break;
+    tile = next;
+  }
+}
+
+// blocks per node of a node launch: the persistent grid's blocks shared among the m nodes
+template <class K>
+static unsigned nodes_grid(K kernel, size_t shm, int64_t ntiles, int m) {
+  const int64_t all = persistent_grid(kernel, shm, ntiles * m);
+  int64_t g = (all + m - 1) / m;
+  if (g > ntiles) g = ntiles;
+  return (unsigned)(g < 1 ? 1 : g);
+}
+
 static int dwt_levels_ok(int64_t n, int level) {
   if (level < 1 || level > DWT_MAX_LEVEL || n <= 0) return 0;
   int64_t len = n;
@@ -972,4 +1057,76 @@ extern "C" int dpz_idwt_sym2(const float* coeffs, int64_t n, int level, float* o
                              dpz_stream_t stream) {
   if (n <= 0) return DPZ_ERR_ARG;
   return dpz_idwt_sym2_tiles(coeffs, n, level, 0, (n + IDWT_TILE - 1) / IDWT_TILE, out, stream);
+}
+
+// ---- m nodes per launch ---------------------------------------------------------------------------
+static inline bool row16(uint64_t p) { return (p & 15u) == 0; }
+
+extern "C" int dpz_dwt_sym2_nodes(int m, const void* table, const void* host_table, int64_t n,
+                                  int level, int accumulate, dpz_stream_t stream) {
+  if (m < 1 || !table || !host_table || n <= 0) return DPZ_ERR_ARG;
+  if (reinterpret_cast<uintptr_t>(table) & 7u) return DPZ_ERR_ARG;
+  const uint64_t* h = static_cast<const uint64_t*>(host_table);
+  const bool wx = h[2] != 0, wd = h[3] != 0;
+  for (int j = 0; j < m; ++j) {  // every check on the host copy, before anything is enqueued
+    const uint64_t* e = h + 4 * (size_t)j;
+    if ((e[2] != 0) != wx || (e[3] != 0) != wd) return DPZ_ERR_ARG;  // one set of outputs
+    if (!e[0] || (wd && !e[1])) return DPZ_ERR_ARG;
+    if (!row16(e[0]) || !row16(e[1]) || !row16(e[2]) || !row16(e[3])) return DPZ_ERR_ARG;
+  }
+  if (accumulate && !wd) return DPZ_ERR_ARG;
+  if (m > 65535) return DPZ_ERR_UNSUPPORTED;
+  if (!dwt_levels_ok(n, level) || level > 4) return DPZ_ERR_UNSUPPORTED;
+  if (!wx && !wd) return DPZ_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Levels LV = make_levels(n, level);
+  LV.rmask = nullptr;
+  const int64_t ntiles = (LV.len[level] + DWT_TL - 1) / DWT_TL;
+  const size_t shm = 2 * (DWT_SPAN0 + DWT_SPAN1) * sizeof(float);
+  const DwtNode* tab = static_cast<const DwtNode*>(table);
+#define DPZ_DWT_NODES_LAUNCH(WXV, WDV, ACV)                                                      \
+  {                                                                                              \
+    const dim3 grid(nodes_grid(dwt_nodes_kernel<WXV, WDV, ACV>, shm, ntiles, m), (unsigned)m);    \
+    DPZ_TIMED(DPZ_KT_DWT, st,                                                                    \
+              dwt_nodes_kernel<WXV, WDV, ACV><<<grid, 256, shm, st>>>(tab, LV, ntiles));         \
+  }
+  if (wx && wd) {
+    if (accumulate) DPZ_DWT_NODES_LAUNCH(true, true, true) else DPZ_DWT_NODES_LAUNCH(true, true, false)
+  } else if (wx) {
+    DPZ_DWT_NODES_LAUNCH(true, false, false)
+  } else {
+    if (accumulate) DPZ_DWT_NODES_LAUNCH(false, true, true) else DPZ_DWT_NODES_LAUNCH(false, true, false)
+  }
+#undef DPZ_DWT_NODES_LAUNCH
+  return DPZ_OK;
+}
+
+extern "C" int dpz_idwt_sym2_nodes(int m, const void* table, const void* host_table, int64_t n,
+                                   int level, dpz_stream_t stream) {
+  if (m < 1 || !table || !host_table || n <= 0) return DPZ_ERR_ARG;
+  if (reinterpret_cast<uintptr_t>(table) & 7u) return DPZ_ERR_ARG;
+  const uint64_t* h = static_cast<const uint64_t*>(host_table);
+  for (int j = 0; j < m; ++j) {
+    const uint64_t* e = h + 2 * (size_t)j;
+    if (!e[0] || !e[1] || !row16(e[0]) || !row16(e[1])) return DPZ_ERR_ARG;
+  }
+  if (m > 65535) return DPZ_ERR_UNSUPPORTED;
+  if (!dwt_levels_ok(n, level) || level > 4) return DPZ_ERR_UNSUPPORTED;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const Levels LV = make_levels(n, level);
+  const int64_t ntiles = (n + IDWT_TILE - 1) / IDWT_TILE;
+  const IdwtNode* tab = static_cast<const IdwtNode*>(table);
+  switch (level) {
+#define DPZ_IDWT_NODES_CASE(LEVN)                                                              \
+  case LEVN: {                                                                                 \
+    const dim3 grid(nodes_grid(idwt_nodes_kernel<LEVN>, 0, ntiles, m), (unsigned)m);            \
+    DPZ_TIMED(DPZ_KT_IDWT, st, idwt_nodes_kernel<LEVN><<<grid, 256, 0, st>>>(tab, LV, ntiles)); \
+    break;                                                                                     \
+  }
+    DPZ_IDWT_NODES_CASE(1) DPZ_IDWT_NODES_CASE(2) DPZ_IDWT_NODES_CASE(3) DPZ_IDWT_NODES_CASE(4)
+#undef DPZ_IDWT_NODES_CASE
+    default:
+      return DPZ_ERR_UNSUPPORTED;
+  }
+  return DPZ_OK;
 }

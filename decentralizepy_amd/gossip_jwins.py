@@ -327,6 +327,11 @@ class JwinsRound(ShardedRound):
             jobs.append((self.wx[j], pays, w, w_self, self.wc[j]))
         self._fork()
         self.ops.fold_all(jobs, self.M)  # node j on stream j % S
+        # ... unless the round qualifies for the library's one-launch fold (every payload sparse,
+        # at most four neighbours): that launch is on the first stream alone, so the other
+        # streams' inverse transforms wait for it here
+        self._join()
+        self._fork()
         for j in range(self.hi - self.lo):
             with self._on(j):
                 self.ops.inverse(self.wc[j], self.N, self.x[j])        # model <- waverec(total)

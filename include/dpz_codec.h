@@ -1050,6 +1050,49 @@ int dpz_topkacc_encode_nodes(int m, const void* node_table, int64_t n, int64_t k
                              void* ws, size_t ws_bytes, dpz_stream_t stream);
 int dpz_topkacc_post_nodes(int m, const void* node_table, int64_t n, dpz_stream_t stream);
 
+/* ---- A JWINS round of a rank's nodes at once (decentralizepy_amd/gossip_jwins_batch.py) ----------
+ * dpz_dwt_sym2_nodes: dpz_dwt_sym2 of m nodes of one length n and one level (1-4) in ONE launch,
+ * the node in the grid's second dimension.  table is a DEVICE array of m entries of 4 64-bit words
+ * {x, x0, coeffs_x or 0, coeffs_diff or 0}; host_table is its HOST copy, on which every check is
+ * made.  Per node the result is bit for bit dpz_dwt_sym2(x, x0, n, level, coeffs_x, coeffs_diff,
+ * accumulate) (the tiles run on the span path at every level, which gives the bits of the level-4
+ * interior path).  Every entry names the same set of outputs; with no output nothing is enqueued.
+ * dpz_idwt_sym2_nodes: dpz_idwt_sym2 of m nodes in ONE launch; entries of 2 words {coeffs, out}.
+ * Both, before anything is enqueued: DPZ_ERR_ARG for m < 1, n < 1, a null or misaligned table, a
+ * null host table, a null required pointer (x; x0 with coeffs_diff; coeffs, out), a row that is
+ * not 16-byte aligned, entries that differ in their outputs, accumulate without coeffs_diff;
+ * DPZ_ERR_UNSUPPORTED for m > 65535, a level outside 1-4 or an n the level does not accept.  The
+ * kernels are timed as "dwt" and "idwt".
+ * dpz_jwins_encode_nodes: the selection of m nodes of one coefficient count n, each with its own
+ * k.  node_table is a DEVICE array of m entries of 8 64-bit words {c, acc, vals_src, counter (or
+ * 0), idx_out, val_out, k, 0}.  Per node, with one fp32 rounding per operation:
+ *   1 <= k <= n  the key is |fl(c_i + acc_i)|, formed once by the first histogram pass and stored
+ *                IN PLACE into the c row.  The k largest keys are selected, ties at the k-th key
+ *                going to the lowest indices; idx = the selection ascending, val = vals_src[idx];
+ *                counter[idx] += 1 (plain stores); acc[idx] = +0; acc is unchanged elsewhere: bit
+ *                for bit dpz_topk_encode(x = c, x0 = NULL, acc, DPZ_ACC_ADD, vals_src, n, k, ...,
+ *                counter, DPZ_TOPK_EXACT).  Exactly k entries are written, the words past them
+ *                are untouched.
+ *   k == 0       a full share: the first pass stores +0 to all of acc and, if val_out != 0,
+ *                copies vals_src to val_out (n floats); c, the counter and idx_out are not
+ *                touched, no other pass reads or writes the node.
+ * A k above n is the caller's error (the table is on the device: the Python wrapper checks its
+ * host values); the kernels then select all n and write nothing outside the node's rows of n.
+ * 16-byte accesses where a node's rows are 16-byte aligned, per element otherwise.  One memset and
+ * nine launches whatever m is, timed under the topk_exact_* names; no float atomics; the result
+ * does not depend on the grid; no host synchronisation.  Finite inputs only.  ws:
+ * dpz_jwins_encode_workspace_bytes(m, n) DEVICE bytes, 4-byte aligned, any content.  Before
+ * anything is enqueued: DPZ_ERR_ARG for m < 1, a null or misaligned table or workspace, n outside
+ * [1, 2^31), a short workspace; DPZ_ERR_UNSUPPORTED for m > 65535.                              */
+int dpz_dwt_sym2_nodes(int m, const void* table, const void* host_table, int64_t n, int level,
+                       int accumulate, dpz_stream_t stream);
+int dpz_idwt_sym2_nodes(int m, const void* table, const void* host_table, int64_t n, int level,
+                        dpz_stream_t stream);
+int64_t dpz_jwins_chunk_elems(void);
+size_t dpz_jwins_encode_workspace_bytes(int m, int64_t n);
+int dpz_jwins_encode_nodes(int m, const void* node_table, int64_t n, void* ws, size_t ws_bytes,
+                           dpz_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
