@@ -858,6 +858,11 @@ def elias_decode(buf, nbytes, nbits, first, count, dtype=torch.int64, workspace=
     ``buf`` is a device uint8 tensor with at least round_up(nbytes, 4) + 16 bytes; ``nbits`` and
     ``first`` come from the stream's trailer; ``count`` bounds the output (the stream encodes at
     most (nbits - 128) + 1 values).
+
+    A stream may hold at most 2^26 code bits (``nbits <= 2**26 + 128``).  A longer one raises
+    CodecError ("unsupported size or configuration") before anything is launched, here and in
+    ``elias_decode_async``.  ``elias_encode`` has no such limit, so it can write a stream that
+    these decoders refuse.
     """
     _require(buf, torch.uint8, "buf")
     if buf.numel() < ((nbytes + 3) // 4) * 4 + 16:
@@ -910,7 +915,11 @@ def elias_decode_async(buf, nbytes, nbits, first, count, status, dtype=torch.int
 def fpz_encode(x, precision=0, out=None, workspace=None):
     """Block-floating stream of a device fp32 vector (csrc/dpz_fpz.hip; the float leg of
     compression/EliasFpzip.py:19-51 at precision 0 and EliasFpzipLossy.py:14-58 at precision p).
-    Returns a device uint8 view of exactly the stream's bytes."""
+    Returns a device uint8 view of exactly the stream's bytes.
+
+    ``precision`` 0 or >= 32 is lossless; 1..31 keeps the top ``precision`` bits of every bit
+    pattern (1..9: sign and leading exponent bits only, no mantissa); a negative precision raises
+    ValueError."""
     _require(x, torch.float32, "x")
     n = x.numel()
     cap = int(_lib.lib().dpz_fpz_max_bytes(n))
@@ -925,14 +934,15 @@ def fpz_encode(x, precision=0, out=None, workspace=None):
     rc = _lib.lib().dpz_fpz_encode(_ptr(x), n, int(precision), _ptr(out), out.numel(),
                                    ctypes.byref(nbytes), _ptr(ws), ws.numel(), _stream(x.device))
     if rc == _lib.DPZ_ERR_UNSUPPORTED:
-        raise ValueError("float precision must be 0 (lossless) or 10..32")
+        raise ValueError("float precision must be >= 0 (0 or >= 32: lossless)")
     check(rc, "dpz_fpz_encode")
     return out[:nbytes.value]
 
 
 def fpz_decode(buf, n, precision, out=None, check_status=True, status=None):
     """Values of a block-floating stream held on the device (a uint8 tensor of the whole stream,
-    4-byte aligned); ``n`` and ``precision`` come from its header.  With ``check_status`` the
+    4-byte aligned); ``n`` and ``precision`` come from its header (any precision >= 0, as
+    ``fpz_encode`` takes; a negative one raises ValueError).  With ``check_status`` the
     call synchronises and raises ValueError on a malformed stream; a caller's ``status`` (device
     int32 word) is OR-ed instead, with no synchronisation."""
     _require(buf, torch.uint8, "buf")
@@ -951,7 +961,7 @@ def fpz_decode(buf, n, precision, out=None, check_status=True, status=None):
     if rc == _lib.DPZ_ERR_ARG:
         raise ValueError("malformed float stream")
     if rc == _lib.DPZ_ERR_UNSUPPORTED:
-        raise ValueError("float precision must be 0 (lossless) or 10..32")
+        raise ValueError("float precision must be >= 0 (0 or >= 32: lossless)")
     check(rc, "dpz_fpz_decode")
     if check_status and int(status.item()) != 0:
         raise ValueError("malformed float stream")

@@ -8,6 +8,10 @@ __device__ __forceinline__ uint32_t f2h(float v) {
   return __builtin_bit_cast(uint16_t, h);
 }
 __device__ __forceinline__ float h2f(uint32_t b) {
+  // A NaN is widened on its bits (sign, payload << 13), as the host's widening (numpy) does: the
+  // hardware conversion would also set the quiet bit of a signalling NaN.
+  if ((b & 0x7C00u) == 0x7C00u && (b & 0x03FFu) != 0u)
+    return __uint_as_float(((b & 0x8000u) << 16) | 0x7F800000u | ((b & 0x03FFu) << 13));
   return (float)__builtin_bit_cast(_Float16, (uint16_t)b);
 }
 

@@ -541,7 +541,9 @@ int dpz_scatter_fill(float* dst, int64_t n, const int32_t* idx, int64_t k, float
 
 /* fp16 value packing (round-to-nearest-even, torch.half semantics) and unpacking.
  * The build's own wire codec for values (BASELINE config C5); the reference's lossy float path
- * is fpzip (compression/EliasFpzipLossy.py:14-58), which is not byte-compatible.             */
+ * is fpzip (compression/EliasFpzipLossy.py:14-58), which is not byte-compatible.
+ * Unpacking equals numpy's half -> float widening on every one of the 65 536 patterns: a NaN
+ * keeps its sign and payload (a signalling NaN is not quieted).                                */
 int dpz_pack_fp16(const float* in, int64_t n, uint16_t* out, dpz_stream_t stream);
 int dpz_unpack_fp16(const uint16_t* in, int64_t n, float* out, dpz_stream_t stream);
 
@@ -585,7 +587,11 @@ int dpz_elias_encode(const int32_t* idx, int64_t k, uint8_t* out, int64_t out_ca
  * nbits/first: the stream's trailer (the caller holds the bytes).  Writes first + running gap
  * sums into out64 (int64, as the reference returns) and/or out32 (either may be NULL); the value
  * count goes to *count_host (host pointer; synchronises).  DPZ_ERR_ARG on a malformed stream,
- * DPZ_ERR_WORKSPACE if the count exceeds out_cap, DPZ_ERR_UNSUPPORTED above 2^26 code bits.    */
+ * DPZ_ERR_WORKSPACE if the count exceeds out_cap.
+ * Limit: a stream may hold at most 2^26 code bits (nbits <= 2^26 + 128: 1024 super maps of 64
+ * chunks of 1024 bits).  Beyond that the call returns DPZ_ERR_UNSUPPORTED before any launch and
+ * writes nothing.  dpz_elias_encode has no such limit, so it can write a stream that this
+ * decoder refuses.                                                                              */
 int dpz_elias_decode(const uint8_t* in, int64_t nbytes, int64_t nbits, int64_t first,
                      int64_t* out64, int32_t* out32, int64_t out_cap, int64_t* count_host,
                      void* ws, size_t ws_bytes, dpz_stream_t stream);
