@@ -1346,13 +1346,13 @@ def mt_mask_batch(seeds, alphas, n, device, mask=None, rank_tab=None, count=None
 
 def _row_ptrs(rows, m):
     """Device addresses of m rows: the rows of a 2-D tensor or the words of a 1-D one (computed
-    from its stride, no views), or a list's tensors."""
+    from its stride, no views), or a list's tensors (None: a zero word)."""
     if rows is None:
         return [0] * m
     if isinstance(rows, torch.Tensor):
         step = rows.stride(0) * rows.element_size()
         return [rows.data_ptr() + j * step for j in range(m)]
-    return [t.data_ptr() for t in rows]
+    return [0 if t is None else t.data_ptr() for t in rows]
 
 
 def _f32_bits(v):
@@ -1826,6 +1826,122 @@ def jwins_encode_nodes(table, n, workspace=None):
     rc = _lib.lib().dpz_jwins_encode_nodes(m, _ptr(table.dev), n, _ptr(workspace),
                                            workspace.numel(), _stream(table.dev.device))
     check(rc, "dpz_jwins_encode_nodes")
+    return workspace
+
+
+class FftNodesTable(_WordTable):
+    """The table of ``rfft_nodes`` (a ``_WordTable``): 4 words per job {x, x0 or 0, out,
+    accumulate}.  A job is a transform: ``x`` / ``x0`` (fp32, n) and ``out`` (complex64,
+    n // 2 + 1) are 2-D tensors (one row per job), lists of per-job tensors, or None for ``x0``
+    (a zero column); ``accumulate`` is one flag for every job or a list of flags."""
+
+    def __init__(self, x, x0, out, accumulate, device):
+        self.m = m = len(x)
+        words, _ = self._words(4 * m)
+        flags = [int(bool(accumulate))] * m if isinstance(accumulate, (bool, int)) \
+            else [int(bool(a)) for a in accumulate]
+        words[:4 * m] = np.array([_row_ptrs(x, m), _row_ptrs(x0, m), _row_ptrs(out, m), flags],
+                                 dtype=np.uint64).T.reshape(-1)
+        self._upload(device)
+
+
+class IfftNodesTable(_WordTable):
+    """The table of ``irfft_nodes`` (a ``_WordTable``): 2 words per job {coeffs, out}."""
+
+    def __init__(self, coeffs, out, device):
+        self.m = m = len(coeffs)
+        words, _ = self._words(2 * m)
+        words[:2 * m] = np.array([_row_ptrs(c, m) for c in (coeffs, out)],
+                                 dtype=np.uint64).T.reshape(-1)
+        self._upload(device)
+
+
+def fft_nodes_workspace(jobs, n, device, workspace=None):
+    """A uint8 device tensor of ``dpz_fft_nodes_workspace_bytes(jobs, n)`` bytes (``workspace``
+    itself when it is large enough); ValueError for a size the batched transforms refuse."""
+    need = int(_lib.lib().dpz_fft_nodes_workspace_bytes(int(jobs), int(n)))
+    if need < 0:
+        raise ValueError(f"batched real FFTs of n={n}: an even n >= 4 with a native plan "
+                         "(fft_native) and jobs >= 1")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+    return workspace
+
+
+def _fft_nodes(name, table, n, workspace, check_rc):
+    _require(table.dev, torch.int64, "table")
+    if workspace is None:
+        need = int(_lib.lib().dpz_fft_nodes_workspace_bytes(table.m, int(n)))
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=table.dev.device)
+    rc = getattr(_lib.lib(), name)(table.m, _ptr(table.dev),
+                                   ctypes.c_void_p(table.host.ctypes.data), int(n),
+                                   _ptr(workspace), workspace.numel(),
+                                   _stream(table.dev.device))
+    if check_rc:
+        check(rc, name)
+    return rc
+
+
+def rfft_nodes(table, n, workspace=None, check_rc=True):
+    """``rfft`` of every job of ``table`` (an ``FftNodesTable``) in ONE launch set, as many
+    launches as one ``rfft`` of that n: per job bit for bit ``rfft(x)``, ``rfft(x - x0)`` (the
+    difference as ``elementwise(SUB)`` rounds it) where the job has an ``x0``, and ``out +=`` that
+    (as ``elementwise(ADD)`` rounds it) where it accumulates.  Even n >= 4 with a native plan.
+    ``workspace``: ``fft_nodes_workspace``'s tensor (allocated here when None).  Returns the
+    library's code (raises unless it is DPZ_OK when ``check_rc``)."""
+    return _fft_nodes("dpz_rfft_nodes", table, n, workspace, check_rc)
+
+
+def irfft_nodes(table, n, workspace=None, check_rc=True):
+    """``irfft`` of every job of ``table`` (an ``IfftNodesTable``) in ONE launch set: per job bit
+    for bit ``irfft(coeffs, n)``; the coefficients are only read."""
+    return _fft_nodes("dpz_irfft_nodes", table, n, workspace, check_rc)
+
+
+def cplx_chunk_elems():
+    """Coefficients one block of ``cplx_encode_nodes``' count and compaction passes covers."""
+    return int(_lib.lib().dpz_cplx_chunk_elems())
+
+
+class CplxEncodeTable(_WordTable):
+    """The node table of ``cplx_encode_nodes`` (a ``_WordTable``): 8 words per node {change, acc
+    or 0, vals_src, key, counter or 0, pair_out, val_out, 0}.  Each argument is a 2-D tensor (one
+    row per node) or a list of per-node tensors; ``acc`` and ``counter`` may be None."""
+
+    def __init__(self, change, acc, vals_src, key, counter, pair_out, val_out, device):
+        self.m = m = len(change)
+        words, _ = self._words(8 * m)
+        cols = (change, acc, vals_src, key, counter, pair_out, val_out, None)
+        words[:8 * m] = np.array([_row_ptrs(c, m) for c in cols], dtype=np.uint64).T.reshape(-1)
+        self._upload(device)
+
+
+def cplx_encode_nodes(table, n, k, acc_mode=DPZ_ACC_NONE, workspace=None):
+    """The FFT plugin's partial share of every node of ``table`` (a ``CplxEncodeTable``) in one
+    launch set: the accumulation step of ``cplx_key`` on the n complex coefficients, the exact
+    top-k of the fp32 key (ties to the lowest indices), and per selected coefficient i,
+    ascending: ``pair_out = (2 i, 2 i + 1)``, ``val_out = vals_src[i]``, ``counter[i] += 1``,
+    ``acc[i] = 0`` where the node has an accumulator.  Nothing is read back.  ``workspace``: a
+    uint8 device tensor kept by the caller (allocated here when None); returned."""
+    m, n, k = table.m, int(n), int(k)
+    if not 1 <= k <= n:
+        raise ValueError(f"k = {k} outside [1, n = {n}]")
+    rows = table.host[:8 * m].reshape(m, 8)
+    if (rows[:, [0, 2, 3, 5, 6]] == 0).any() or (acc_mode != DPZ_ACC_NONE
+                                                 and (rows[:, 1] == 0).any()):
+        raise ValueError("a node table with a null row: change, vals_src, key, pair_out and "
+                         "val_out of every node, acc with an accumulating mode")
+    if (rows[:, [0, 1, 2, 5, 6]] & 7).any() or (rows[:, [3, 4]] & 3).any():
+        raise ValueError("a misaligned row: complex rows and pair_out on 8 bytes, key and "
+                         "counter on 4")
+    _require(table.dev, torch.int64, "table")
+    need = int(_lib.lib().dpz_cplx_encode_workspace_bytes(m, n))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=table.dev.device)
+    rc = _lib.lib().dpz_cplx_encode_nodes(m, _ptr(table.dev), n, k, int(acc_mode),
+                                          _ptr(workspace), workspace.numel(),
+                                          _stream(table.dev.device))
+    check(rc, "dpz_cplx_encode_nodes")
     return workspace
 
 

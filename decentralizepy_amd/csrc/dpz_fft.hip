@@ -158,38 +158,60 @@ struct FtPass {
   FtTw tw;
 };
 
+// where a pass reads and writes: the FtPass's own fields (ft_io), or a job's rows (the batched
+// kernels, which take them from the job table)
+struct FtIo {
+  const float2* in;
+  const float* in_re;
+  float2* out;
+  float* out_re;
+  int load_mode;
+};
+__device__ __forceinline__ FtIo ft_io(const FtPass& a) {
+  return FtIo{a.in, a.in_re, a.out, a.out_re, a.load_mode};
+}
+
 __device__ __forceinline__ float2 ft_mi(float2 z, bool inv);
 __device__ __forceinline__ float2 ft_c2r_pair(float2 p, float2 q, uint32_t kk, const FtTw& tw);
 __device__ __forceinline__ float2 ft_r2c_pair(float2 p, float2 q, uint32_t kk, const FtTw& tw);
 
-__device__ __forceinline__ float2 ft_load(const FtPass& a, int64_t i) {
-  if (a.load_mode == 1) return make_float2(a.in_re[i], 0.0f);
-  if (a.load_mode == 3) {  // Z[i] from X[i] and X[M - i] (Im X[0], Im X[M] dropped), as the
-    float2 p = a.in[i], q = a.in[a.n_aux - i];  // separate pre pass computes it
+// NODES (the batched kernels only): load mode 4, z[i] - z0[i] per component (the real vectors x and
+// x0 as n / 2 pairs: one fp32 subtraction per element, dpz_elementwise(SUB)'s), z0 behind in_re
+template <bool NODES>
+__device__ __forceinline__ float2 ft_load(const FtPass& a, const FtIo& io, int64_t i) {
+  if constexpr (NODES) {
+    if (io.load_mode == 4) {
+      const float2 u = io.in[i], v = reinterpret_cast<const float2*>(io.in_re)[i];
+      return make_float2(u.x - v.x, u.y - v.y);
+    }
+  }
+  if (io.load_mode == 1) return make_float2(io.in_re[i], 0.0f);
+  if (io.load_mode == 3) {  // Z[i] from X[i] and X[M - i] (Im X[0], Im X[M] dropped), as the
+    float2 p = io.in[i], q = io.in[a.n_aux - i];  // separate pre pass computes it
     if (i == 0) {
       p.y = 0.0f;
       q.y = 0.0f;
     }
     return ft_c2r_pair(p, q, (uint32_t)i, a.tw);
   }
-  if (a.load_mode == 2) {
+  if (io.load_mode == 2) {
     const int64_t h = a.n_aux / 2 + 1;
     if (i < h) {
-      const float2 v = a.in[i];
+      const float2 v = io.in[i];
       return i == 0 ? make_float2(v.x, 0.0f) : v;
     }
-    const float2 v = a.in[a.n_aux - i];
+    const float2 v = io.in[a.n_aux - i];
     return make_float2(v.x, -v.y);
   }
-  return a.in[i];
+  return io.in[i];
 }
 
-__device__ __forceinline__ void ft_store(const FtPass& a, int64_t o, float2 v) {
+__device__ __forceinline__ void ft_store(const FtPass& a, const FtIo& io, int64_t o, float2 v) {
   switch (a.store_mode) {
-    case 1: a.out[o] = make_float2(v.x * a.scale, v.y * a.scale); break;
-    case 2: a.out_re[o] = v.x * a.scale; break;
-    case 3: if (o < a.n_aux) a.out[o] = v; break;
-    default: a.out[o] = v;
+    case 1: io.out[o] = make_float2(v.x * a.scale, v.y * a.scale); break;
+    case 2: io.out_re[o] = v.x * a.scale; break;
+    case 3: if (o < a.n_aux) io.out[o] = v; break;
+    default: io.out[o] = v;
   }
 }
 
@@ -411,8 +433,8 @@ __device__ __forceinline__ void ft_sub_any(const float2* src, float2* dst, int B
 // through registers run with ONE LDS buffer (sub-passes staged in registers): 72 VGPRs and half
 // the LDS, so more blocks per CU; the others (11, 13, other primes) ping-pong two buffers
 extern __shared__ float2 ft_lds[];
-template <bool IP>
-__device__ __forceinline__ void ft_pass_body(const FtPass& a) {
+template <bool IP, bool NODES = false>
+__device__ __forceinline__ void ft_pass_body(const FtPass& a, const FtIo& io) {
   const int B = a.B, R = a.R, RP = a.RP;
   const int t = threadIdx.x;
   // pair mode: slots c < H hold columns jf0 + c (jf <= S / 2), slots H + c their mirrors S - jf
@@ -454,7 +476,7 @@ __device__ __forceinline__ void ft_pass_body(const FtPass& a) {
       for (int i = 0; i < FT_REG_ELEMS / FT_THREADS; ++i) {
         const int r = r0 + i * rs;
         const bool ok = cv && r < R;
-        v[i] = ft_load(a, ok ? j + (int64_t)r * a.S : j0);
+        v[i] = ft_load<NODES>(a, io, ok ? j + (int64_t)r * a.S : j0);
         const uint32_t e = ok ? (uint32_t)(((uint64_t)r * k) * twm) : 0u;
         w[i] = ft_root(a.tw, e, inv);
       }
@@ -465,7 +487,7 @@ __device__ __forceinline__ void ft_pass_body(const FtPass& a) {
       }
     } else if (cv) {
       for (int r = r0; r < R; r += rs) {
-        float2 v = ft_load(a, j + (int64_t)r * a.S);
+        float2 v = ft_load<NODES>(a, io, j + (int64_t)r * a.S);
         if (k && r) v = ft_cmul(v, ft_root(a.tw, (uint32_t)(((uint64_t)r * k) * twm), inv));
         src[c * RP + r] = v;
       }
@@ -520,13 +542,13 @@ __device__ __forceinline__ void ft_pass_body(const FtPass& a) {
         const float2 zp = src[cf * RP + m];
         const int64_t o = j + (int64_t)m * a.S;
         if (o == 0) {
-          a.out[0] = make_float2(zp.x + zp.y, 0.0f);
-          a.out[M] = make_float2(zp.x - zp.y, 0.0f);
+          io.out[0] = make_float2(zp.x + zp.y, 0.0f);
+          io.out[M] = make_float2(zp.x - zp.y, 0.0f);
           continue;
         }
         const float2 zq = j == 0 ? src[cf * RP + (R - m)] : src[(cf + H) * RP + (R - 1 - m)];
-        a.out[o] = ft_r2c_pair(zp, zq, (uint32_t)o, a.tw);
-        a.out[M - o] = ft_r2c_pair(zq, zp, (uint32_t)(M - o), a.tw);
+        io.out[o] = ft_r2c_pair(zp, zq, (uint32_t)o, a.tw);
+        io.out[M - o] = ft_r2c_pair(zq, zp, (uint32_t)(M - o), a.tw);
       }
     }
     return;
@@ -544,12 +566,12 @@ __device__ __forceinline__ void ft_pass_body(const FtPass& a) {
       for (int i = 0; i < NE; ++i) {
         const int e = t + i * FT_THREADS;
         const int c = e / R, m = e - c * R;
-        if (c < cols) ft_store(a, (j0 + c) * R + m, v[i]);
+        if (c < cols) ft_store(a, io, (j0 + c) * R + m, v[i]);
       }
     } else {
       for (int e = t; e < cols * R; e += FT_THREADS) {
         const int c = e / R, m = e - c * R;
-        ft_store(a, (j0 + c) * R + m, src[c * RP + m]);
+        ft_store(a, io, (j0 + c) * R + m, src[c * RP + m]);
       }
     }
   } else {
@@ -568,11 +590,11 @@ __device__ __forceinline__ void ft_pass_body(const FtPass& a) {
 #pragma unroll
         for (int i = 0; i < NE; ++i) {
           const int m = m0 + i * rs;
-          if (m < R) ft_store(a, base + (int64_t)m * a.p, v[i]);
+          if (m < R) ft_store(a, io, base + (int64_t)m * a.p, v[i]);
         }
       }
     } else if (c < cols) {
-      for (int m = m0; m < R; m += rs) ft_store(a, base + (int64_t)m * a.p, src[c * RP + m]);
+      for (int m = m0; m < R; m += rs) ft_store(a, io, base + (int64_t)m * a.p, src[c * RP + m]);
     }
   }
 }
@@ -582,9 +604,57 @@ __device__ __forceinline__ void ft_pass_body(const FtPass& a) {
 // compiles (125 VGPRs, 4 waves)
 __global__ void __launch_bounds__(FT_THREADS) __attribute__((amdgpu_waves_per_eu(DPZ_FT_IP_WAVES, 8)))
 ft_pass_ip_kernel(FtPass a) {
-  ft_pass_body<true>(a);
+  ft_pass_body<true>(a, ft_io(a));
 }
-__global__ void __launch_bounds__(FT_THREADS) ft_pass_kernel(FtPass a) { ft_pass_body<false>(a); }
+__global__ void __launch_bounds__(FT_THREADS) ft_pass_kernel(FtPass a) {
+  ft_pass_body<false>(a, ft_io(a));
+}
+
+// ---- `jobs` transforms of one length per launch (dpz_rfft_nodes / dpz_irfft_nodes): the job in
+// the grid's second dimension, its rows from a DEVICE table, the same pass bodies.  Job y's
+// buffers: A, its scratch row; B, its output row - or, for an accumulating forward job, whose
+// output holds the sum, a second scratch row (the first again when the plan has one pass).  The
+// passes alternate as ft_run's do (A = bufA, B = bufB), the last landing in B.
+struct FtNodes {
+  const uint64_t* tab;  // forward: {x, x0 or 0, out, accumulate}; inverse: {coeffs, out}
+  char* ws;             // row A of job y at ws + y * pitch, row B at ws + offB + y * pitch
+  size_t pitch, offB;
+  int inverse;
+  int s, npass;         // this pass
+};
+
+__device__ __forceinline__ float2* ft_job_b(const FtNodes& nd, const uint64_t* e) {
+  if (nd.inverse) return reinterpret_cast<float2*>(e[1]);
+  return e[3] ? reinterpret_cast<float2*>(nd.ws + nd.offB + (size_t)blockIdx.y * nd.pitch)
+              : reinterpret_cast<float2*>(e[2]);
+}
+
+template <bool IP>
+__device__ __forceinline__ void ft_pass_nodes_body(const FtPass& a, const FtNodes& nd) {
+  const uint64_t* e = nd.tab + (size_t)blockIdx.y * (nd.inverse ? 2 : 4);
+  float2* A = reinterpret_cast<float2*>(nd.ws + (size_t)blockIdx.y * nd.pitch);
+  float2* B = ft_job_b(nd, e);
+  FtIo io{nullptr, nullptr, nullptr, nullptr, a.load_mode};  // the kernel argument stays as it is
+  if (nd.s == 0) {
+    io.in = reinterpret_cast<const float2*>(e[0]);
+    if (!nd.inverse && e[1]) {  // uniform over the block
+      io.load_mode = 4;
+      io.in_re = reinterpret_cast<const float*>(e[1]);
+    }
+  } else {
+    io.in = ((nd.npass - nd.s) & 1) ? A : B;
+  }
+  io.out = (nd.s == nd.npass - 1 || !((nd.npass - 1 - nd.s) & 1)) ? B : A;
+  ft_pass_body<IP, true>(a, io);
+}
+
+__global__ void __launch_bounds__(FT_THREADS) __attribute__((amdgpu_waves_per_eu(DPZ_FT_IP_WAVES, 8)))
+ft_pass_ip_nodes_kernel(FtPass a, FtNodes nd) {
+  ft_pass_nodes_body<true>(a, nd);
+}
+__global__ void __launch_bounds__(FT_THREADS) ft_pass_nodes_kernel(FtPass a, FtNodes nd) {
+  ft_pass_nodes_body<false>(a, nd);
+}
 
 // even n, forward: X[k] = ((Z[k] + conj Z[M-k]) - i W_n^k (Z[k] - conj Z[M-k])) / 2 for the pair
 // (k, M - k), k <= M / 2; Z read from `z` (may equal out)
@@ -602,6 +672,36 @@ __global__ void __launch_bounds__(256) ft_r2c_post_kernel(const float2* z, float
     const float2 xm = ft_r2c_pair(b, a, (uint32_t)(M - k), tw);
     out[k] = xk;
     if (M - k != k) out[M - k] = xm;
+  }
+}
+
+// the same pairing of job blockIdx.y: Z from its row B (its output row unless it accumulates);
+// an accumulating job stores out[k] = fl(out[k] + X[k]) per component (dpz_elementwise(ADD)'s
+// sum, the zero imaginary parts of X[0] and X[M] included)
+__global__ void __launch_bounds__(256) ft_r2c_post_nodes_kernel(FtNodes nd, int64_t M, FtTw tw) {
+  const uint64_t* e = nd.tab + (size_t)blockIdx.y * 4;
+  const float2* z = ft_job_b(nd, e);
+  float2* out = reinterpret_cast<float2*>(e[2]);
+  const bool accum = e[3] != 0;
+  auto put = [&](int64_t i, float2 v) {
+    if (accum) {
+      const float2 o = out[i];
+      v = make_float2(o.x + v.x, o.y + v.y);
+    }
+    out[i] = v;
+  };
+  for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k <= M / 2; k += (int64_t)gridDim.x * 256) {
+    if (k == 0) {
+      const float2 z0 = z[0];
+      put(0, make_float2(z0.x + z0.y, 0.0f));
+      put(M, make_float2(z0.x - z0.y, 0.0f));
+      continue;
+    }
+    const float2 a = z[k], b = z[M - k];
+    const float2 xk = ft_r2c_pair(a, b, (uint32_t)k, tw);
+    const float2 xm = ft_r2c_pair(b, a, (uint32_t)(M - k), tw);
+    put(k, xk);
+    if (M - k != k) put(M - k, xm);
   }
 }
 
@@ -745,16 +845,25 @@ static int ft_tables(uint32_t nt, FtTw* tw) {
 }
 
 static bool g_ft_lds_set = false;
+static bool g_ft_nodes_lds_set = false;
 
 // the plan's passes: pass 1 reads (in, in_re, load_mode), the last writes (out, out_re,
 // store_mode, scale); the others alternate between bufA and bufB so that the last lands in out
 static int ft_run(const FtPlan& pl, const FtTw& tw, bool inv, const float2* in, const float* in_re,
                   int load_mode, float2* out, float* out_re, int store_mode, float scale,
                   int64_t n_aux, float2* bufA, float2* bufB, hipStream_t st,
-                  bool* pair_last = nullptr) {
+                  bool* pair_last = nullptr, const FtNodes* nodes = nullptr, int jobs = 0) {
   const bool want_pair = pair_last && *pair_last;
   if (pair_last) *pair_last = false;
-  if (!g_ft_lds_set) {
+  if (nodes && !g_ft_nodes_lds_set) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(ft_pass_nodes_kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(ft_pass_ip_nodes_kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+      return DPZ_ERR_INTERNAL;
+    g_ft_nodes_lds_set = true;
+  }
+  if (!nodes && !g_ft_lds_set) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(ft_pass_kernel),
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void*>(ft_pass_ip_kernel),
@@ -819,7 +928,17 @@ static int ft_run(const FtPlan& pl, const FtTw& tw, bool inv, const float2* in, 
     }
     const size_t lds = ((ip ? 1 : 2) * (size_t)B * a.RP + (a.R <= FT_PACK ? a.R : 0)) *
                        sizeof(float2);
-    if (ip) {
+    if (nodes) {  // the job's rows come from its table entry (ft_pass_nodes_body)
+      FtNodes nd = *nodes;
+      nd.s = s;
+      nd.npass = pl.npass;
+      const dim3 grid((unsigned)blocks, (unsigned)jobs);
+      if (ip) {
+        DPZ_TIMED(DPZ_KT_FFT, st, ft_pass_ip_nodes_kernel<<<grid, FT_THREADS, lds, st>>>(a, nd));
+      } else {
+        DPZ_TIMED(DPZ_KT_FFT, st, ft_pass_nodes_kernel<<<grid, FT_THREADS, lds, st>>>(a, nd));
+      }
+    } else if (ip) {
       DPZ_TIMED(DPZ_KT_FFT, st, ft_pass_ip_kernel<<<(unsigned)blocks, FT_THREADS, lds, st>>>(a));
     } else {
       DPZ_TIMED(DPZ_KT_FFT, st, ft_pass_kernel<<<(unsigned)blocks, FT_THREADS, lds, st>>>(a));
@@ -1009,6 +1128,85 @@ extern "C" int dpz_irfft(float* coeffs, int64_t n, float* out, void* ws, size_t 
   if (rc != DPZ_OK) return rc;
   DPZ_TIMED(DPZ_KT_FFT_SCALE, st, scale_kernel<<<grid_for(n), 256, 0, st>>>(out, n, 1.0f / (float)n));
   return DPZ_OK;
+}
+
+// ---- `jobs` transforms per launch set --------------------------------------------------------------
+// one scratch row of M = n / 2 complex per job, and a second one where the plan has two or more
+// passes (an accumulating job cannot run its passes through its output row); rows on 256 bytes
+static size_t ft_nodes_pitch(int64_t n) { return align256((size_t)(n / 2) * sizeof(float2)); }
+
+// the plan of a batched call: DPZ_OK, or why the size is refused
+static int ft_nodes_plan(int64_t n, FtPlan* pl) {
+  if (n < 4 || n % 2 != 0) return DPZ_ERR_UNSUPPORTED;
+  if (!ft_native_plan(n, pl) || pl->npass < 1) return DPZ_ERR_UNSUPPORTED;
+  return DPZ_OK;
+}
+
+extern "C" int64_t dpz_fft_nodes_workspace_bytes(int jobs, int64_t n) {
+  FtPlan pl;
+  if (jobs < 1 || ft_nodes_plan(n, &pl) != DPZ_OK) return -1;
+  return (int64_t)((size_t)jobs * ft_nodes_pitch(n) * (pl.npass >= 2 ? 2 : 1) + 256);
+}
+
+static int ft_nodes_args(int jobs, const void* table, const void* host_table, int words,
+                         int64_t n, const void* ws, size_t ws_bytes, FtPlan* pl, FtNodes* nd) {
+  if (jobs < 1 || !table || !host_table || (reinterpret_cast<uintptr_t>(table) & 7u))
+    return DPZ_ERR_ARG;
+  const int rc = ft_nodes_plan(n, pl);
+  if (rc != DPZ_OK) return rc;
+  const uint64_t* h = static_cast<const uint64_t*>(host_table);
+  for (int j = 0; j < jobs; ++j) {  // every check on the host copy, before anything is enqueued
+    const uint64_t* e = h + (size_t)words * j;
+    if (words == 4) {
+      if (!e[0] || !e[2] || ((e[0] | e[1] | e[2]) & 7u) || e[3] > 1) return DPZ_ERR_ARG;
+    } else if (!e[0] || !e[1] || ((e[0] | e[1]) & 7u)) {
+      return DPZ_ERR_ARG;
+    }
+  }
+  if (jobs > 65535) return DPZ_ERR_UNSUPPORTED;
+  if (!ws || (int64_t)ws_bytes < dpz_fft_nodes_workspace_bytes(jobs, n)) return DPZ_ERR_WORKSPACE;
+  nd->tab = static_cast<const uint64_t*>(table);
+  nd->ws = reinterpret_cast<char*>(ft_align(const_cast<void*>(ws), 0));
+  nd->pitch = ft_nodes_pitch(n);
+  nd->offB = pl->npass >= 2 ? (size_t)jobs * nd->pitch : 0;
+  nd->inverse = words == 2;
+  nd->s = nd->npass = 0;
+  return DPZ_OK;
+}
+
+extern "C" int dpz_rfft_nodes(int jobs, const void* table, const void* host_table, int64_t n,
+                              void* ws, size_t ws_bytes, dpz_stream_t stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  FtPlan pl;
+  FtNodes nd;
+  int rc = ft_nodes_args(jobs, table, host_table, 4, n, ws, ws_bytes, &pl, &nd);
+  if (rc != DPZ_OK) return rc;
+  FtTw tw;
+  rc = ft_tables((uint32_t)n, &tw);
+  if (rc != DPZ_OK) return rc;
+  const int64_t M = n / 2;
+  rc = ft_run(pl, tw, false, nullptr, nullptr, 0, nullptr, nullptr, 0, 1.0f, 0, nullptr, nullptr,
+              st, nullptr, &nd, jobs);
+  if (rc != DPZ_OK) return rc;
+  const dim3 grid(grid_for(M / 2 + 1), (unsigned)jobs);
+  DPZ_TIMED(DPZ_KT_FFT, st, ft_r2c_post_nodes_kernel<<<grid, 256, 0, st>>>(nd, M, tw));
+  return DPZ_OK;
+}
+
+extern "C" int dpz_irfft_nodes(int jobs, const void* table, const void* host_table, int64_t n,
+                               void* ws, size_t ws_bytes, dpz_stream_t stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  FtPlan pl;
+  FtNodes nd;
+  int rc = ft_nodes_args(jobs, table, host_table, 2, n, ws, ws_bytes, &pl, &nd);
+  if (rc != DPZ_OK) return rc;
+  FtTw tw;
+  rc = ft_tables((uint32_t)n, &tw);
+  if (rc != DPZ_OK) return rc;
+  // as the single call: the first pass forms Z[k] from X[k] and X[M - k] as it loads (load mode
+  // 3; the coefficients are only read), 1/n in the last pass's stores
+  return ft_run(pl, tw, true, nullptr, nullptr, 3, nullptr, nullptr, 1, 1.0f / (float)n, n / 2,
+                nullptr, nullptr, st, nullptr, &nd, jobs);
 }
 
 extern "C" int dpz_cplx_key(const float* change, float* acc, int acc_mode, int64_t m, float* key,

@@ -1,6 +1,6 @@
 """What the whole-topology round engines (gossip.py, gossip_jwins.py, gossip_jwins_batch.py,
 gossip_subsampling.py, gossip_epidemic.py, gossip_choco.py, gossip_quant.py, gossip_stc.py,
-gossip_topkacc.py) share:
+gossip_topkacc.py, gossip_fft.py) share:
 ``ShardedRound``, the sharding of the nodes over the ranks, and ``PackedRowRound``, the packed row
 per node that one all-gather exchanges."""
 import math

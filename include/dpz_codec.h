@@ -1099,6 +1099,51 @@ size_t dpz_jwins_encode_workspace_bytes(int m, int64_t n);
 int dpz_jwins_encode_nodes(int m, const void* node_table, int64_t n, void* ws, size_t ws_bytes,
                            dpz_stream_t stream);
 
+/* ---- An FFT round of a rank's nodes at once (decentralizepy_amd/gossip_fft.py) -------------------
+ * dpz_rfft_nodes: `jobs` forward real FFTs of one even length n >= 4 with a native plan
+ * (dpz_fft_native), in one launch set of as many launches as one dpz_rfft of that n: the job is in
+ * the grid's second dimension of the pass and pairing kernels.  table is a DEVICE array of `jobs`
+ * entries of 4 64-bit words {x, x0 or 0, out, accumulate (0 / 1)}; host_table is its HOST copy, on
+ * which every check is made.  x, x0: n reals; out: n / 2 + 1 complex.  With x0 the first pass
+ * loads fl(x[i] - x0[i]) (dpz_elementwise(DPZ_EW_SUB)'s difference); with accumulate the pairing
+ * pass stores out[k] = fl(out[k] + X[k]) per component (dpz_elementwise(DPZ_EW_ADD)'s sum).  Per
+ * job the result is bit for bit that of the single calls.  x and x0 are only read.
+ * dpz_irfft_nodes: `jobs` inverse transforms; entries of 2 words {coeffs, out}: n / 2 + 1 complex,
+ * only read, and n reals; per job bit for bit dpz_irfft's result.
+ * ws: dpz_fft_nodes_workspace_bytes(jobs, n) DEVICE bytes (-1 for a size the calls refuse): one
+ * scratch row of n / 2 complex per job, and a second one per job where the plan has two or more
+ * passes (an accumulating job cannot run its passes through its output row).
+ * Both, before anything is enqueued and with nothing written: DPZ_ERR_ARG for jobs < 1, a null or
+ * misaligned table, a null host table, a null x / out / coeffs, a row that is not 8-byte aligned,
+ * an accumulate word above 1; DPZ_ERR_UNSUPPORTED for an odd n, n < 4, an n whose plan is not
+ * native (hipFFT sizes) and jobs > 65535; DPZ_ERR_WORKSPACE for a null or short workspace.  The
+ * kernels are timed as "fft".
+ * dpz_cplx_encode_nodes: the exact top-k of |c| over the n complex coefficients of m nodes, one k
+ * (1 <= k <= n) and one DPZ_ACC_* mode per call.  node_table is a DEVICE array of m entries of 8
+ * 64-bit words {change, acc (or 0 with DPZ_ACC_NONE), vals_src, key, counter (or 0), pair_out,
+ * val_out, 0}: change, acc, vals_src n complex; key n fp32 (scratch); counter n int32; pair_out
+ * 2 k int32 (8-byte aligned); val_out k complex.  The first pass does dpz_cplx_key's accumulation
+ * step and stores key[i] = sqrtf(re re + im im) (one rounding per operation); the k largest keys
+ * are selected, ties at the k-th key going to the lowest indices; per selected i, ascending:
+ * pair_out = (2 i, 2 i + 1), val_out = vals_src[i], counter[i] += 1, acc[i] = (+0, +0) when acc
+ * is set: bit for bit dpz_cplx_key, the exact dpz_topk_encode of the key, dpz_cplx_gather and
+ * dpz_cplx_pair_indices.  One memset and nine launches whatever m is, timed under the topk_exact_*
+ * names; no float atomics; the result does not depend on the grid; no host synchronisation.
+ * Finite inputs only.  ws: dpz_cplx_encode_workspace_bytes(m, n) DEVICE bytes, 4-byte aligned.
+ * Before anything is enqueued: DPZ_ERR_ARG for m < 1, a null or misaligned table or workspace, n
+ * outside [1, 2^30), k outside [1, n], an unknown mode, a short workspace; DPZ_ERR_UNSUPPORTED
+ * for m > 65535.  The table's rows are the caller's to get right (the Python wrapper checks its
+ * host copy).                                                                                    */
+int64_t dpz_fft_nodes_workspace_bytes(int jobs, int64_t n);
+int dpz_rfft_nodes(int jobs, const void* table, const void* host_table, int64_t n, void* ws,
+                   size_t ws_bytes, dpz_stream_t stream);
+int dpz_irfft_nodes(int jobs, const void* table, const void* host_table, int64_t n, void* ws,
+                    size_t ws_bytes, dpz_stream_t stream);
+int64_t dpz_cplx_chunk_elems(void);
+size_t dpz_cplx_encode_workspace_bytes(int m, int64_t n);
+int dpz_cplx_encode_nodes(int m, const void* node_table, int64_t n, int64_t k, int acc_mode,
+                          void* ws, size_t ws_bytes, dpz_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
