@@ -122,6 +122,8 @@ SIGNATURES = {
                                   ctypes.POINTER(_c_void_p), ctypes.POINTER(_i64),
                                   ctypes.POINTER(ctypes.c_float), ctypes.c_float, _int, _c_void_p,
                                   _c_void_p, _size, _c_void_p]),
+    "dpz_debug_fold_batch_plan": (_int, [_int, _i64, ctypes.POINTER(_int), ctypes.POINTER(_i64),
+                                         ctypes.POINTER(_int), _int, _int, ctypes.POINTER(_int)]),
     "dpz_debug_fold_plan": (_int, [_i64, _int, ctypes.POINTER(_i64), ctypes.POINTER(_int),
                                    ctypes.POINTER(ctypes.c_float), _int, _int, _int,
                                    ctypes.POINTER(_int)]),

@@ -46,7 +46,7 @@ extern "C" int dpz_topk_encode_batch(int m, const float* const* x, const float* 
 }
 
 namespace dpz {
-// dpz_fold_walk.hip: every node's fold in one launch per FW_BATCH nodes (1 = the batch does not qualify)
+// dpz_fold_walk.hip: every node's fold in one launch per table of nodes (1 = the batch does not qualify)
 int fold_batch_walk(int m, const float* const* local, float* const* out, int64_t n,
                     const int* n_payloads, const int32_t* const* idx, const float* const* vals,
                     const int64_t* k, const float* w, const float* w_self, int flags,
@@ -62,8 +62,9 @@ extern "C" int dpz_decode_average_batch(int m, const float* const* local, float*
   if (m < 0 || n_streams < 1 || !local || !out || !n_payloads || !ws || !streams) return DPZ_ERR_ARG;
   for (int j = 0; j < m; ++j)
     if (n_payloads[j] < 0) return DPZ_ERR_ARG;
-  // a round of plain few-payload folds (the C4 gossip round): one walk launch per 22 nodes on
-  // streams[0] instead of one per node (dpz_fold_walk.hip fold_batch_walk)
+  // a round of plain folds: one walk launch per table of nodes on streams[0] instead of one per
+  // node (dpz_fold_walk.hip fold_batch_walk: the C4 gossip round's few sparse payloads per node
+  // in one launch per 22 nodes; any payload count, dense payloads mixed in, in one per table)
   {
     const int rc = dpz::fold_batch_walk(m, local, out, n, n_payloads, idx, vals, k, w, w_self,
                                         flags, static_cast<hipStream_t>(streams[0]), nullptr, 0);

@@ -37,7 +37,7 @@ import ctypes
 
 import torch
 
-from .gossip_round import ShardedRound, shard  # noqa: F401 - shard is part of this module's surface
+from .gossip_round import ShardedRound, shard, up4  # noqa: F401 - shard is part of this module's surface
 
 
 def read_edges(path):
@@ -101,8 +101,10 @@ class GossipRound(ShardedRound):
         # between, guarded on the device by the encodes' status words (_step_guarded)
         self.guarded = guarded
         self.k = round(alpha * self.N)
-        self.x = x_init.contiguous().clone()
-        self.x0 = x_init.contiguous().clone()  # init_model of every owned node
+        # rows up4(N) words apart: 16-byte aligned at any N, as the one-launch folds need them
+        # (N a multiple of 4: the plain contiguous matrix)
+        self.x = self._model_rows(x_init)
+        self.x0 = self._model_rows(x_init)  # init_model of every owned node
         # sliced_counter (HIP, node-batched encodes): every node's shared_parameters_counter as 32
         # bit planes plus a selection mask per round (DPZ_TOPK_SLICED: compact writes the mask
         # and ripple-adds it to the planes instead of k scattered counter atomics); ``counter``
@@ -201,7 +203,7 @@ class GossipRound(ShardedRound):
             row = 4 * self.N
             g = int(hbm_budget // (2 * row * (world + 1))) if hbm_budget != float("inf") else self.per
             self.rs_group = max(1, min(self.per, g))
-        self.out = torch.empty_like(self.x)
+        self.out = self._model_rows(x_init, fill=False)
         self.leg_times = None
         # the encodes' sampled-path status words (padded to `per`: the all-gathered guard of the
         # folds, _step_guarded); the injected CPU encodes never miss and leave them 0
@@ -711,11 +713,19 @@ class GossipRound(ShardedRound):
         np.add(tab["idx0"], tab["ring_mask"] * off, out=tab["idx_now"])
         return tab
 
+    def _model_rows(self, x_init, fill=True):
+        rows = torch.empty(x_init.shape[0], up4(self.N), dtype=x_init.dtype,
+                           device=x_init.device)[:, :self.N]
+        if fill:
+            rows.copy_(x_init)
+        return rows
+
     def fold_all(self, guard=None):
         """Every owned node's Metro-Hastings fold.  guard (HIP, DEVICE int32): the round's
         encode status words; the one-launch fold then writes nothing if any is nonzero
-        (dpz_decode_average_batch_guarded).  Returns False, with nothing enqueued, when the
-        guarded launch does not apply to this round (the caller checks the encodes first)."""
+        (dpz_decode_average_batch_guarded: nodes of any degree, one launch per table of nodes).
+        Returns False, with nothing enqueued, when the guarded launch does not apply to this
+        round (N < 1024, a node without neighbours; the caller checks the encodes first)."""
         nodes = range(self.hi - self.lo)
         if guard is not None and not self._hip:  # the injected folds: the guard read on the host
             if bool(guard.any()):

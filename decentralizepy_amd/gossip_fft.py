@@ -24,7 +24,8 @@ A ``step()`` is, whatever the node count and with no host synchronisation:
    the float-pair form ``(2 i, 2 i + 1)`` the fold reads (2 k words) beside the k complex values
    (2 k words), so no rank converts indices after the exchange;
 4. the batched fold over the float view of ``fx`` into ``ch`` (n = 2 M):
-   ``dpz_decode_average_batch_guarded`` with a zero guard word, else (a fifth neighbour)
+   ``dpz_decode_average_batch_guarded`` with a zero guard word (any number of neighbours: one
+   launch per table of nodes), else (2 M < 1024, a node without neighbours)
    ``dpz_decode_average_batch`` on the same stream;
 5. ONE ``dpz_irfft_nodes`` launch set into ``x``;
 6. with ``accumulate_averaging_changes``: ONE accumulating ``dpz_rfft_nodes`` launch set of m
@@ -242,7 +243,7 @@ class FftRound(ShardedRound):
         rc = L.dpz_decode_average_batch_guarded(
             m, ft["local"], ft["out"], 2 * M, ft["np"], ft["idx"], ft["val"], ft["k"], ft["w"],
             ft["w_self"], _lib.DPZ_FOLD_SELF, self._guard.data_ptr(), 1, stream)
-        if rc == _lib.DPZ_ERR_UNSUPPORTED:  # a fifth neighbour: node after node
+        if rc == _lib.DPZ_ERR_UNSUPPORTED:  # 2 M < 1024 or a node without neighbours: node after node
             rc = L.dpz_decode_average_batch(
                 m, ft["local"], ft["out"], 2 * M, ft["np"], ft["idx"], ft["val"], ft["k"], ft["w"],
                 ft["w_self"], _lib.DPZ_FOLD_SELF, (ctypes.c_void_p * 1)(self._dws.data_ptr()),

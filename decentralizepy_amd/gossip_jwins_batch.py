@@ -23,8 +23,9 @@ count:
 * ONE all-gather of one int32 buffer per rank, ``[idx block | val block]``, the block sizes being
   the round's maxima over the ranks, which every rank derives from the replayed draws;
 * the fold into the ``wc`` rows: ``dpz_decode_average_batch_guarded`` with a zero guard word when
-  the round qualifies (every payload sparse, at most four neighbours), else
-  ``dpz_decode_average_batch`` on the same stream (a dense payload or a fifth neighbour);
+  the round qualifies (any number of neighbours, partial and full shares mixed: one launch per
+  table of nodes), else ``dpz_decode_average_batch`` on the same stream (M < 1024, a node
+  without neighbours);
 * ONE ``dpz_idwt_sym2_nodes`` launch into ``x``, ONE accumulating ``dpz_dwt_sym2_nodes`` launch,
   ONE copy of all rows of ``x`` into ``x0``.
 
@@ -245,7 +246,7 @@ class JwinsBatchRound(ShardedRound):
         rc = L.dpz_decode_average_batch_guarded(
             m, ft["local"], ft["out"], M, ft["np"], idx_a, val_a, k_a, ft["w"], ft["w_self"],
             _lib.DPZ_FOLD_SELF, self._guard.data_ptr(), 1, stream)
-        if rc == _lib.DPZ_ERR_UNSUPPORTED:  # a dense payload or a fifth neighbour: node after node
+        if rc == _lib.DPZ_ERR_UNSUPPORTED:  # M < 1024 or a node without neighbours: node after node
             rc = L.dpz_decode_average_batch(
                 m, ft["local"], ft["out"], M, ft["np"], idx_a, val_a, k_a, ft["w"], ft["w_self"],
                 _lib.DPZ_FOLD_SELF, (ctypes.c_void_p * 1)(self._dws.data_ptr()),

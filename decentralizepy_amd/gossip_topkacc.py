@@ -181,7 +181,7 @@ class TopKAccRound(PackedRowRound):
         rc = _lib.lib().dpz_decode_average_batch_guarded(
             self.m, tab["local"], tab["out"], self.N, ft["np"], ft["idx"], ft["val"], ft["k"],
             ft["w"], ft["w_self"], flags, self.guard.data_ptr(), self.guard.numel(), stream)
-        if rc == _lib.DPZ_ERR_UNSUPPORTED:  # a node with more than 4 neighbours: node after node
+        if rc == _lib.DPZ_ERR_UNSUPPORTED:  # N < 1024 or a node without neighbours: node after node
             if self._dws is None:
                 self._dws = codec.Workspace(self.device)
             dws = self._dws.get_decode(self.N, ft["maxp"])

@@ -342,6 +342,17 @@ int dpz_decode_average(const float* local, int64_t n, int n_payloads, const int3
 int dpz_debug_fold_plan(int64_t n, int n_payloads, const int64_t* k, const int* dense,
                         const float* w, int flags, int fresh, int aligned, int* plan_out);
 
+/* Diagnostic: how dpz_decode_average_batch / dpz_decode_average_batch_guarded fold a batch of m
+ * nodes, computed on the host with no device call by the function the library itself launches
+ * by.  n_payloads[m]; k / dense: the nodes' payloads flattened in node order (dense[i] != 0:
+ * payload i is dense, NULL: none); aligned: every local, out and dense row is 16-byte aligned
+ * (and out[j] != local[j]).  plan_out[DPZ_FOLD_BATCH_PLAN_INTS] = { path (0: node after node,
+ * 1: the <= 4 sparse payloads kernel, 2: the any-degree kernel), launches (kernel launches of
+ * the call), nodes of the first launch, passes (ceil(largest payload count / 16)) }.          */
+#define DPZ_FOLD_BATCH_PLAN_INTS 4
+int dpz_debug_fold_batch_plan(int m, int64_t n, const int* n_payloads, const int64_t* k,
+                              const int* dense, int flags, int aligned, int* plan_out);
+
 /* Replace decode of a GLOBAL payload into one rank's slice of a model sharded over ranks
  * (SURVEY §8e "one tensor, decode: no collective"; reference sharing/PartialModel.py:292-295
  * `T[idx] = params` restricted to the slice): local / out hold global elements
@@ -393,15 +404,24 @@ int dpz_decode_average_batch(int m, const float* const* local, float* const* out
                              const float* const* vals, const int64_t* k, const float* w,
                              const float* w_self, int flags, void* const* ws, size_t ws_bytes,
                              int n_streams, const dpz_stream_t* streams);
-/* dpz_decode_average_batch's one-launch fold of a gossip round (every node 1..4 sparse payloads,
- * flags within DPZ_FOLD_SELF | DPZ_FOLD_ALSO_LOCAL, 16-byte aligned rows, out[j] != local[j]) on
- * ONE stream, guarded by the round's encodes: each launch first reads guard[0, guard_n) (DEVICE
+/* dpz_decode_average_batch's one-launch fold of a gossip round on ONE stream, guarded by the
+ * round's encodes.  The batch qualifies when m >= 2, 1024 <= n < 2^31 - 1024, flags are within
+ * DPZ_FOLD_SELF | DPZ_FOLD_ALSO_LOCAL, every row (local, out, a dense payload's values) is
+ * 16-byte aligned, out[j] != local[j], every node has at least one payload and every payload is
+ * either sparse with 1 <= k <= n or dense (idx NULL, k == n); a dense payload excludes
+ * DPZ_FOLD_ALSO_LOCAL (it may be another node's local row).  Nodes of 1..4 sparse payloads
+ * only: one launch per 22 nodes.  Otherwise: one launch per table of nodes (a node takes one
+ * slot plus one per payload of 146: 22 nodes of 4 payloads, 8 nodes of 16), a node's payloads
+ * past the 16th in further launches that continue its total from out (the self term and the
+ * DPZ_FOLD_ALSO_LOCAL copy with its last 16).  Each launch first reads guard[0, guard_n) (DEVICE
  * int32, e.g. dpz_topk_encode_nodes' status words) and, if any word is nonzero, writes nothing
  * (out and, with DPZ_FOLD_ALSO_LOCAL, local unchanged), so the caller checks the encodes once
  * after the round instead of between encode and fold, and re-runs the round's folds after
  * re-running a missed encode exactly.  DPZ_ERR_UNSUPPORTED (nothing enqueued) when the batch
- * does not qualify.  Replaces the reference's encode -> send -> receive -> _averaging order of
- * every node (sharing/PartialModel.py:188-255, sharing/Sharing.py:156-190), run side by side. */
+ * does not qualify.  dpz_decode_average_batch takes the same launches (unguarded, on
+ * streams[0]) for a qualifying batch, and folds any other node after node.  Replaces the
+ * reference's encode -> send -> receive -> _averaging order of every node
+ * (sharing/PartialModel.py:188-255, sharing/Sharing.py:156-190), run side by side.            */
 int dpz_decode_average_batch_guarded(int m, const float* const* local, float* const* out,
                                      int64_t n, const int* n_payloads,
                                      const int32_t* const* idx, const float* const* vals,

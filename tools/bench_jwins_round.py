@@ -7,7 +7,9 @@ at level 4, ``metadata_cap = 0.5``:
   ref96     ``96_regular.edges`` x N = 89,834 (the reference's CIFAR LeNet): 96 small models, a
             node's kernels take microseconds, the round is bound by the host;
   c3_16     ``regular_16.edges`` x N = 25,000,000 (DESIGN's JWINS C3 shape (b)): the kernels take
-            the time.
+            the time;
+  sw96      ``96_nodes_smallworld.edges`` x N = 89,834: 3 to 10 neighbours per node, the fold's
+            any-degree launches (not among the default shapes).
 
 Two variants of the same round, alternated round by round in one process, from the same models
 and the same seeded "training" step between rounds, so their states stay equal in every bit
@@ -29,7 +31,7 @@ over; the range over the runs is reported, and a speed-up as the range [baseline
 max, baseline max / engine min]: a range that contains 1 is no difference.  Prints one JSON line
 per shape.
 
-    python tools/bench_jwins_round.py [--shapes ref96,c3_16] [--rounds 50] [--runs 3]
+    python tools/bench_jwins_round.py [--shapes ref96,c3_16,sw96] [--rounds 50] [--runs 3]
 """
 import argparse
 import json
@@ -48,7 +50,8 @@ from decentralizepy_amd.gossip_jwins_batch import JwinsBatchRound  # noqa: E402
 
 ALPHAS = [0.1, 0.15, 0.2, 0.25, 0.3, 0.4, 1.0]  # tutorial/JWINS/config.ini
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-SHAPES = {"ref96": ("96_regular.edges", 89_834), "c3_16": ("regular_16.edges", 25_000_000)}
+SHAPES = {"ref96": ("96_regular.edges", 89_834), "c3_16": ("regular_16.edges", 25_000_000),
+          "sw96": ("96_nodes_smallworld.edges", 89_834)}
 
 
 class Baseline:

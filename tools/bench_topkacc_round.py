@@ -3,7 +3,8 @@
 
 Shape: the 96 nodes of ``96_regular.edges`` on one rank (no collective is part of the timing),
 N = 11,000,000, alpha in {0.01, 0.1}, both accumulation modes (``--edges``, ``--n``, ``--alphas``,
-``--modes``).  The state is 5 x nodes x 4 N bytes per variant (x, x0, acc, counter, the fold's
+``--modes``; ``--shape sw96``: ``96_nodes_smallworld.edges``, 3 to 10 neighbours per node, at
+N = 89,834, the shape of the same name of ``bench_jwins_round.py``).  The state is 5 x nodes x 4 N bytes per variant (x, x0, acc, counter, the fold's
 output); it is checked against the free HBM before anything is allocated.
 
 Two variants of the same round, alternated round by round in one process, from the same models
@@ -34,7 +35,7 @@ the ENGINE's algorithmic bytes per node, k = round(alpha N):
 ``copy_tb_per_s`` is a device-to-device copy of 1 GiB timed in the same process.  Prints one JSON
 line per (alpha, mode).
 
-    python tools/bench_topkacc_round.py [--n 11000000] [--alphas 0.01,0.1] [--modes acc,avg]
+    python tools/bench_topkacc_round.py [--n 11000000] [--alphas 0.01,0.1] [--modes acc,avg] [--shape sw96]
 """
 import argparse
 import json
@@ -215,6 +216,9 @@ def run_config(args, adj, dev, alpha, avg, copy):
         raise SystemExit("the engine's and the baseline's states differ")
 
 
+SHAPES = {"sw96": ("96_nodes_smallworld.edges", 89_834)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=11_000_000)
@@ -224,10 +228,15 @@ def main():
     ap.add_argument("--nodes", type=int, default=0,
                     help="keep only the first NODES nodes of the graph (0: all); lower it if the "
                          "state does not fit the device")
+    ap.add_argument("--shape", choices=sorted(SHAPES), default=None,
+                    help="a named (edges, n) pair instead of --edges and --n")
     ap.add_argument("--rounds", type=int, default=50)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=2)
     args = ap.parse_args()
+    if args.shape:
+        args.edges, args.n = os.path.join(ROOT, "tests", "golden", SHAPES[args.shape][0]), \
+            SHAPES[args.shape][1]
     if not torch.cuda.is_available():
         raise SystemExit("bench_topkacc_round needs a ROCm GPU; there is no CPU path")
     dev = torch.device("cuda:0")
