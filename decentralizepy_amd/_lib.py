@@ -278,6 +278,12 @@ SIGNATURES = {
     "dpz_fft_nodes_workspace_bytes": (_i64, [_int, _i64]),
     "dpz_rfft_nodes": (_int, [_int, _c_void_p, _c_void_p, _i64, _c_void_p, _size, _c_void_p]),
     "dpz_irfft_nodes": (_int, [_int, _c_void_p, _c_void_p, _i64, _c_void_p, _size, _c_void_p]),
+    "dpz_fft_chirp_length": (_i64, [_i64]),
+    "dpz_fft_chirp_nodes_workspace_bytes": (_i64, [_int, _i64]),
+    "dpz_rfft_chirp_nodes": (_int, [_int, _c_void_p, _c_void_p, _i64, _c_void_p, _size,
+                                    _c_void_p]),
+    "dpz_irfft_chirp_nodes": (_int, [_int, _c_void_p, _c_void_p, _i64, _c_void_p, _size,
+                                     _c_void_p]),
     "dpz_cplx_chunk_elems": (_i64, []),
     "dpz_cplx_encode_workspace_bytes": (_size, [_int, _i64]),
     "dpz_cplx_encode_nodes": (_int, [_int, _c_void_p, _i64, _i64, _int, _c_void_p, _size,

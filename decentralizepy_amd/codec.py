@@ -979,10 +979,17 @@ def _fft_ws(n, workspace, device):
     return buf
 
 
-def rfft(x, out=None, workspace=None):
+def _chirp_ws(n, workspace, device):
+    workspace = workspace or Workspace(device)
+    buf = workspace.cbuf = fft_chirp_nodes_workspace(1, n, device, getattr(workspace, "cbuf", None))
+    return buf
+
+
+def rfft(x, out=None, workspace=None, chirp=False):
     """``torch.fft.rfft(x)`` of a device fp32 vector (reference sharing/JWINS/FFT.py:12-25):
     the native mixed-radix kernels, or hipFFT for a size with a prime factor above 4096
-    (``fft_native(n)``); returns complex64[n // 2 + 1]."""
+    (``fft_native(n)``); returns complex64[n // 2 + 1].  ``chirp=True`` (even n >= 4) runs the
+    vector as a one-job table through ``rfft_chirp_nodes`` instead."""
     _require(x, torch.float32, "x")
     n = x.numel()
     if out is None:
@@ -990,6 +997,10 @@ def rfft(x, out=None, workspace=None):
     _require(out, torch.complex64, "out")
     if out.numel() != n // 2 + 1:
         raise ValueError("out must hold n // 2 + 1 complex values")
+    if chirp:
+        rfft_chirp_nodes(FftNodesTable([x], None, [out], False, x.device), n,
+                         _chirp_ws(n, workspace, x.device))
+        return out
     ws = _fft_ws(n, workspace, x.device)
     rc = _lib.lib().dpz_rfft(_ptr(x), n, _ptr(out), _ptr(ws), ws.numel(), _stream(x.device))
     check(rc, "dpz_rfft")
@@ -1001,9 +1012,10 @@ def fft_native(n):
     return bool(_lib.lib().dpz_fft_native(int(n)))
 
 
-def irfft(coeffs, n, out=None, workspace=None):
+def irfft(coeffs, n, out=None, workspace=None, chirp=False):
     """``torch.fft.irfft(coeffs, n)`` (1/n normalisation; reference sharing/JWINS/FFT.py:301).
-    ``coeffs`` (complex64[n // 2 + 1]) is overwritten."""
+    ``coeffs`` (complex64[n // 2 + 1]) is overwritten.  ``chirp=True`` (even n >= 4) runs a
+    one-job table through ``irfft_chirp_nodes`` instead, which only reads ``coeffs``."""
     _require(coeffs, torch.complex64, "coeffs")
     n = int(n)
     if coeffs.numel() != n // 2 + 1:
@@ -1011,6 +1023,10 @@ def irfft(coeffs, n, out=None, workspace=None):
     if out is None:
         out = torch.empty(n, dtype=torch.float32, device=coeffs.device)
     _require(out, torch.float32, "out")
+    if chirp:
+        irfft_chirp_nodes(IfftNodesTable([coeffs], [out], coeffs.device), n,
+                          _chirp_ws(n, workspace, coeffs.device))
+        return out
     ws = _fft_ws(n, workspace, coeffs.device)
     rc = _lib.lib().dpz_irfft(_ptr(coeffs), n, _ptr(out), _ptr(ws), ws.numel(),
                               _stream(coeffs.device))
@@ -1896,6 +1912,54 @@ def irfft_nodes(table, n, workspace=None, check_rc=True):
     """``irfft`` of every job of ``table`` (an ``IfftNodesTable``) in ONE launch set: per job bit
     for bit ``irfft(coeffs, n)``; the coefficients are only read."""
     return _fft_nodes("dpz_irfft_nodes", table, n, workspace, check_rc)
+
+
+def fft_chirp_length(n):
+    """The padded length P of the chirp-z transforms of n reals (the smallest 7-smooth number
+    >= n - 1); 0 for an n they refuse (odd, below 4, above 2**30)."""
+    return int(_lib.lib().dpz_fft_chirp_length(int(n)))
+
+
+def fft_chirp_nodes_workspace(jobs, n, device, workspace=None):
+    """A uint8 device tensor of ``dpz_fft_chirp_nodes_workspace_bytes(jobs, n)`` bytes
+    (``workspace`` itself when it is large enough); ValueError for a size the chirp-z transforms
+    refuse."""
+    need = int(_lib.lib().dpz_fft_chirp_nodes_workspace_bytes(int(jobs), int(n)))
+    if need < 0:
+        raise ValueError(f"batched chirp-z real FFTs of n={n}: an even n in [4, 2**30] and "
+                         "jobs >= 1")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+    return workspace
+
+
+def _fft_chirp_nodes(name, table, n, workspace, check_rc):
+    _require(table.dev, torch.int64, "table")
+    if workspace is None:
+        need = int(_lib.lib().dpz_fft_chirp_nodes_workspace_bytes(table.m, int(n)))
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=table.dev.device)
+    rc = getattr(_lib.lib(), name)(table.m, _ptr(table.dev),
+                                   ctypes.c_void_p(table.host.ctypes.data), int(n),
+                                   _ptr(workspace), workspace.numel(),
+                                   _stream(table.dev.device))
+    if check_rc:
+        check(rc, name)
+    return rc
+
+
+def rfft_chirp_nodes(table, n, workspace=None, check_rc=True):
+    """``rfft_nodes``' transforms of ``table`` (an ``FftNodesTable``) by the chirp-z algorithm:
+    every even n in [4, 2**30], one launch set whatever the job count.  The results agree with
+    ``rfft_nodes``' to rounding (not bit for bit); the x0 subtraction and the accumulating store
+    round as ``elementwise(SUB)`` / ``elementwise(ADD)`` do.  ``workspace``:
+    ``fft_chirp_nodes_workspace``'s tensor (allocated here when None)."""
+    return _fft_chirp_nodes("dpz_rfft_chirp_nodes", table, n, workspace, check_rc)
+
+
+def irfft_chirp_nodes(table, n, workspace=None, check_rc=True):
+    """``irfft_nodes``' transforms of ``table`` (an ``IfftNodesTable``) by the chirp-z algorithm;
+    the coefficients are only read."""
+    return _fft_chirp_nodes("dpz_irfft_chirp_nodes", table, n, workspace, check_rc)
 
 
 def cplx_chunk_elems():

@@ -29,9 +29,11 @@
 
 #include <algorithm>
 #include <cmath>
+#include <complex>
 #include <functional>
 #include <map>
 #include <mutex>
+#include <set>
 #include <tuple>
 #include <vector>
 
@@ -656,6 +658,23 @@ __global__ void __launch_bounds__(FT_THREADS) ft_pass_nodes_kernel(FtPass a, FtN
   ft_pass_nodes_body<false>(a, nd);
 }
 
+// ---- `jobs` complex transforms of one length between workspace rows (the chirp-z calls' DFT_P):
+// the FtPass's own in / out are job 0's rows, job blockIdx.y's lie `pitch` bytes further each
+__device__ __forceinline__ FtIo ft_io_row(const FtPass& a, size_t pitch) {
+  FtIo io = ft_io(a);
+  const size_t off = (size_t)blockIdx.y * pitch;
+  io.in = reinterpret_cast<const float2*>(reinterpret_cast<const char*>(a.in) + off);
+  io.out = reinterpret_cast<float2*>(reinterpret_cast<char*>(a.out) + off);
+  return io;
+}
+__global__ void __launch_bounds__(FT_THREADS) __attribute__((amdgpu_waves_per_eu(DPZ_FT_IP_WAVES, 8)))
+ft_pass_ip_rows_kernel(FtPass a, size_t pitch) {
+  ft_pass_body<true>(a, ft_io_row(a, pitch));
+}
+__global__ void __launch_bounds__(FT_THREADS) ft_pass_rows_kernel(FtPass a, size_t pitch) {
+  ft_pass_body<false>(a, ft_io_row(a, pitch));
+}
+
 // even n, forward: X[k] = ((Z[k] + conj Z[M-k]) - i W_n^k (Z[k] - conj Z[M-k])) / 2 for the pair
 // (k, M - k), k <= M / 2; Z read from `z` (may equal out)
 __global__ void __launch_bounds__(256) ft_r2c_post_kernel(const float2* z, float2* out, int64_t M,
@@ -846,16 +865,38 @@ static int ft_tables(uint32_t nt, FtTw* tw) {
 
 static bool g_ft_lds_set = false;
 static bool g_ft_nodes_lds_set = false;
+// the rows kernels' dynamic-LDS attribute is a property of the device's code object: the devices
+// that have it (guarded by g_ft_mu)
+static std::set<int> g_ft_rows_lds_devs;
+
+static int ft_rows_lds_attr() {
+  int dev = 0;
+  DPZ_HIP_TRY(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(g_ft_mu);
+  if (g_ft_rows_lds_devs.count(dev)) return DPZ_OK;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(ft_pass_rows_kernel),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void*>(ft_pass_ip_rows_kernel),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+    return DPZ_ERR_INTERNAL;
+  g_ft_rows_lds_devs.insert(dev);
+  return DPZ_OK;
+}
 
 // the plan's passes: pass 1 reads (in, in_re, load_mode), the last writes (out, out_re,
-// store_mode, scale); the others alternate between bufA and bufB so that the last lands in out
+// store_mode, scale); the others alternate between bufA and bufB so that the last lands in out.
+// rows_pitch != 0: `jobs` transforms, the pointers being job 0's rows (ft_pass_rows_kernel)
 static int ft_run(const FtPlan& pl, const FtTw& tw, bool inv, const float2* in, const float* in_re,
                   int load_mode, float2* out, float* out_re, int store_mode, float scale,
                   int64_t n_aux, float2* bufA, float2* bufB, hipStream_t st,
-                  bool* pair_last = nullptr, const FtNodes* nodes = nullptr, int jobs = 0) {
+                  bool* pair_last = nullptr, const FtNodes* nodes = nullptr, int jobs = 0,
+                  size_t rows_pitch = 0) {
   const bool want_pair = pair_last && *pair_last;
   if (pair_last) *pair_last = false;
-  if (nodes && !g_ft_nodes_lds_set) {
+  if (rows_pitch) {
+    const int rc = ft_rows_lds_attr();
+    if (rc != DPZ_OK) return rc;
+  } else if (nodes && !g_ft_nodes_lds_set) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(ft_pass_nodes_kernel),
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void*>(ft_pass_ip_nodes_kernel),
@@ -863,7 +904,7 @@ static int ft_run(const FtPlan& pl, const FtTw& tw, bool inv, const float2* in, 
       return DPZ_ERR_INTERNAL;
     g_ft_nodes_lds_set = true;
   }
-  if (!nodes && !g_ft_lds_set) {
+  if (!nodes && !rows_pitch && !g_ft_lds_set) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(ft_pass_kernel),
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void*>(ft_pass_ip_kernel),
@@ -928,7 +969,15 @@ static int ft_run(const FtPlan& pl, const FtTw& tw, bool inv, const float2* in, 
     }
     const size_t lds = ((ip ? 1 : 2) * (size_t)B * a.RP + (a.R <= FT_PACK ? a.R : 0)) *
                        sizeof(float2);
-    if (nodes) {  // the job's rows come from its table entry (ft_pass_nodes_body)
+    if (rows_pitch) {
+      const dim3 grid((unsigned)blocks, (unsigned)jobs);
+      if (ip) {
+        DPZ_TIMED(DPZ_KT_FFT, st,
+                  ft_pass_ip_rows_kernel<<<grid, FT_THREADS, lds, st>>>(a, rows_pitch));
+      } else {
+        DPZ_TIMED(DPZ_KT_FFT, st, ft_pass_rows_kernel<<<grid, FT_THREADS, lds, st>>>(a, rows_pitch));
+      }
+    } else if (nodes) {  // the job's rows come from its table entry (ft_pass_nodes_body)
       FtNodes nd = *nodes;
       nd.s = s;
       nd.npass = pl.npass;
@@ -1148,12 +1197,8 @@ extern "C" int64_t dpz_fft_nodes_workspace_bytes(int jobs, int64_t n) {
   return (int64_t)((size_t)jobs * ft_nodes_pitch(n) * (pl.npass >= 2 ? 2 : 1) + 256);
 }
 
-static int ft_nodes_args(int jobs, const void* table, const void* host_table, int words,
-                         int64_t n, const void* ws, size_t ws_bytes, FtPlan* pl, FtNodes* nd) {
-  if (jobs < 1 || !table || !host_table || (reinterpret_cast<uintptr_t>(table) & 7u))
-    return DPZ_ERR_ARG;
-  const int rc = ft_nodes_plan(n, pl);
-  if (rc != DPZ_OK) return rc;
+// the rows of a job table's host copy (4 words: forward, 2: inverse)
+static int ft_nodes_rows(int jobs, const void* host_table, int words) {
   const uint64_t* h = static_cast<const uint64_t*>(host_table);
   for (int j = 0; j < jobs; ++j) {  // every check on the host copy, before anything is enqueued
     const uint64_t* e = h + (size_t)words * j;
@@ -1163,6 +1208,17 @@ static int ft_nodes_args(int jobs, const void* table, const void* host_table, in
       return DPZ_ERR_ARG;
     }
   }
+  return DPZ_OK;
+}
+
+static int ft_nodes_args(int jobs, const void* table, const void* host_table, int words,
+                         int64_t n, const void* ws, size_t ws_bytes, FtPlan* pl, FtNodes* nd) {
+  if (jobs < 1 || !table || !host_table || (reinterpret_cast<uintptr_t>(table) & 7u))
+    return DPZ_ERR_ARG;
+  int rc = ft_nodes_plan(n, pl);
+  if (rc != DPZ_OK) return rc;
+  rc = ft_nodes_rows(jobs, host_table, words);
+  if (rc != DPZ_OK) return rc;
   if (jobs > 65535) return DPZ_ERR_UNSUPPORTED;
   if (!ws || (int64_t)ws_bytes < dpz_fft_nodes_workspace_bytes(jobs, n)) return DPZ_ERR_WORKSPACE;
   nd->tab = static_cast<const uint64_t*>(table);
@@ -1207,6 +1263,309 @@ extern "C" int dpz_irfft_nodes(int jobs, const void* table, const void* host_tab
   // 3; the coefficients are only read), 1/n in the last pass's stores
   return ft_run(pl, tw, true, nullptr, nullptr, 3, nullptr, nullptr, 1, 1.0f / (float)n, n / 2,
                 nullptr, nullptr, st, nullptr, &nd, jobs);
+}
+
+// ---- chirp-z (Bluestein) real FFTs: every even n, `jobs` per launch set -------------------------
+// The complex length L = n / 2 of an even-n real FFT as a cyclic convolution of a padded length P
+// that has a plan: with w_j = exp(-i pi j^2 / L) and b the conjugate chirp wrapped to length P
+// (b[m] = b[P - m] = conj w_m, m < L),
+//   DFT_L(z)[k] = w_k * sum_j (z_j w_j) b[k - j] = w_k * IDFT_P(DFT_P(a) . DFT_P(b))[k],
+// a_j = z_j w_j (j < L), 0 up to P.  The inverse DFT_L is the same chain with conj w and
+// conj DFT_P(b) (b is symmetric, so DFT_P(conj b) = conj DFT_P(b)).  Launches, whatever `jobs` is:
+// one that forms a (the x0 subtraction / the c2r pairing in its loads), the forward passes of P
+// between the job's two workspace rows, the product with Bhat = DFT_P(b) / P, the inverse passes,
+// and one that applies w_k and the even-n pairing (the accumulating store) / conj w_k and 1 / n.
+// The existing pass kernels' loads and stores are left as they are: the chirp, the padding and
+// the product are elementwise launches of their own.
+namespace dpz {
+
+struct FtChirp {
+  const uint64_t* tab;  // forward: {x, x0 or 0, out, accumulate}; inverse: {coeffs, out}
+  char* row;            // job y's row of P complex at row + y * pitch
+  size_t pitch;
+  const float2* w;      // w_j, j < L
+  const float2* bhat;   // DFT_P(b) / P
+  int64_t L, P;
+  int inverse;
+  float scale;          // inverse: 1 / n
+};
+
+__device__ __forceinline__ float2 ft_conj_if(float2 v, bool c) {
+  return c ? make_float2(v.x, -v.y) : v;
+}
+
+// a[i] = z[i] w_i (forward: z the n reals as L pairs, minus x0's where the job has one) or
+// Z[i] conj w_i (inverse: Z[i] from X[i] and X[L - i], load mode 3's arithmetic) for i < L, 0 for
+// L <= i < P
+__global__ void __launch_bounds__(256) ft_chirp_pre_kernel(FtChirp c, FtTw twn) {
+  const uint64_t* e = c.tab + (size_t)blockIdx.y * (c.inverse ? 2 : 4);
+  float2* a = reinterpret_cast<float2*>(c.row + (size_t)blockIdx.y * c.pitch);
+  const float2* in = reinterpret_cast<const float2*>(e[0]);
+  const float2* in0 = c.inverse ? nullptr : reinterpret_cast<const float2*>(e[1]);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < c.P; i += (int64_t)gridDim.x * 256) {
+    float2 v = make_float2(0.0f, 0.0f);
+    if (i < c.L) {
+      const float2 w = c.w[i];
+      if (c.inverse) {
+        float2 p = in[i], q = in[c.L - i];
+        if (i == 0) {
+          p.y = 0.0f;
+          q.y = 0.0f;
+        }
+        v = ft_cmul(ft_c2r_pair(p, q, (uint32_t)i, twn), make_float2(w.x, -w.y));
+      } else {
+        float2 u = in[i];
+        if (in0) {
+          const float2 u0 = in0[i];
+          u = make_float2(u.x - u0.x, u.y - u0.y);
+        }
+        v = ft_cmul(u, w);
+      }
+    }
+    a[i] = v;
+  }
+}
+
+// row[i] *= Bhat[i] (inverse: conj Bhat[i]), i < P
+__global__ void __launch_bounds__(256) ft_chirp_mul_kernel(FtChirp c) {
+  float2* a = reinterpret_cast<float2*>(c.row + (size_t)blockIdx.y * c.pitch);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < c.P; i += (int64_t)gridDim.x * 256)
+    a[i] = ft_cmul(a[i], ft_conj_if(c.bhat[i], c.inverse != 0));
+}
+
+// forward: Z[k] = y[k] w_k, then ft_r2c_post_nodes_kernel's pairing and store
+__global__ void __launch_bounds__(256) ft_chirp_post_r2c_kernel(FtChirp c, FtTw twn) {
+  const uint64_t* e = c.tab + (size_t)blockIdx.y * 4;
+  const float2* y = reinterpret_cast<const float2*>(c.row + (size_t)blockIdx.y * c.pitch);
+  float2* out = reinterpret_cast<float2*>(e[2]);
+  const bool accum = e[3] != 0;
+  const int64_t M = c.L;
+  auto put = [&](int64_t i, float2 v) {
+    if (accum) {
+      const float2 o = out[i];
+      v = make_float2(o.x + v.x, o.y + v.y);
+    }
+    out[i] = v;
+  };
+  for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k <= M / 2; k += (int64_t)gridDim.x * 256) {
+    if (k == 0) {
+      const float2 z0 = ft_cmul(y[0], c.w[0]);
+      put(0, make_float2(z0.x + z0.y, 0.0f));
+      put(M, make_float2(z0.x - z0.y, 0.0f));
+      continue;
+    }
+    const float2 a = ft_cmul(y[k], c.w[k]), b = ft_cmul(y[M - k], c.w[M - k]);
+    const float2 xk = ft_r2c_pair(a, b, (uint32_t)k, twn);
+    const float2 xm = ft_r2c_pair(b, a, (uint32_t)(M - k), twn);
+    put(k, xk);
+    if (M - k != k) put(M - k, xm);
+  }
+}
+
+// inverse: the n reals as L pairs, out[k] = y[k] conj w_k / n
+__global__ void __launch_bounds__(256) ft_chirp_post_c2r_kernel(FtChirp c) {
+  const uint64_t* e = c.tab + (size_t)blockIdx.y * 2;
+  const float2* y = reinterpret_cast<const float2*>(c.row + (size_t)blockIdx.y * c.pitch);
+  float2* out = reinterpret_cast<float2*>(e[1]);
+  for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < c.L; k += (int64_t)gridDim.x * 256) {
+    const float2 w = c.w[k];
+    const float2 z = ft_cmul(y[k], make_float2(w.x, -w.y));
+    out[k] = make_float2(z.x * c.scale, z.y * c.scale);
+  }
+}
+
+// the padded length of an even n in [4, 2^30]: the smallest 7-smooth P >= n - 1 (2 L - 1); 0 for
+// any other n.  The next power of two (DPZ_FFT_CHIRP_POW2=1, diagnostic build) measured slower on
+// an MI355X at LeNet's 89,834 (P = 131,072 against 90,000, three passes either way): 96 jobs
+// 3.95 ms against 2.78 ms, one job 99 us against 90 us - the passes move P complex each
+constexpr int FT_CHIRP_POW2 = 0;
+static int64_t ft_chirp_len(int64_t n) {
+  if (n < 4 || n % 2 != 0 || n > (int64_t(1) << 30)) return 0;
+  const int64_t lo = n - 1;
+  int64_t best = 1;
+  while (best < lo) best <<= 1;
+  if (DPZ_KNOB_INT(FFT_CHIRP_POW2, FT_CHIRP_POW2) == 0) {
+    for (int64_t p7 = 1; p7 < best; p7 *= 7)
+      for (int64_t p5 = p7; p5 < best; p5 *= 5)
+        for (int64_t p3 = p5; p3 < best; p3 *= 3) {
+          int64_t p = p3;
+          while (p < lo) p <<= 1;
+          if (p < best) best = p;
+        }
+  }
+  return best;
+}
+
+// exact DFT_n of in[0], in[stride], ... into out[0 .. n) in double (decimation in time over the
+// smallest prime factor, each at most 7 here); root[e * rs] = W_n^e
+using FtCd = std::complex<double>;
+static void ft_host_dft(const FtCd* in, FtCd* out, int64_t n, int64_t stride, const FtCd* root,
+                        int64_t rs) {
+  if (n == 1) {
+    out[0] = in[0];
+    return;
+  }
+  int r = 2;
+  while (n % r != 0) ++r;
+  const int64_t m = n / r;
+  for (int q = 0; q < r; ++q) ft_host_dft(in + q * stride, out + q * m, m, stride * r, root, rs * r);
+  FtCd y[8], t[8];
+  for (int64_t k = 0; k < m; ++k) {
+    for (int q = 0; q < r; ++q) y[q] = out[q * m + k] * root[(q * k) * rs];
+    for (int s = 0; s < r; ++s) {
+      FtCd acc = y[0];
+      for (int q = 1; q < r; ++q) acc += y[q] * root[(int64_t)((q * s) % r) * m * rs];
+      t[s] = acc;
+    }
+    for (int s = 0; s < r; ++s) out[k + s * m] = t[s];
+  }
+}
+
+// the chirp w (L complex) and Bhat = DFT_P(b) / P (P complex) of a size, cached per (device, n, P)
+// beside the twiddles.  w_j: the exponent j^2 reduced mod 2 L in integers, the angle and its
+// cosine / sine in long double, rounded once to fp32.  Bhat: b from the unrounded chirp, its DFT
+// in double on the host, divided by P and rounded once to fp32 - so the table carries half an ulp
+// per entry where a device-built one would carry the forward plan's own fp32 error
+struct FtChirpTab {
+  float2* w = nullptr;
+  float2* bhat = nullptr;
+};
+static std::map<std::tuple<int, int64_t, int64_t>, FtChirpTab> g_ft_chirp_tabs;
+
+static int ft_chirp_tables(int64_t n, int64_t P, FtChirpTab* out) {
+  int dev = 0;
+  DPZ_HIP_TRY(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(g_ft_mu);
+  const auto key = std::make_tuple(dev, n, P);
+  auto it = g_ft_chirp_tabs.find(key);
+  if (it == g_ft_chirp_tabs.end()) {
+    const int64_t L = n / 2;
+    const long double pi = 3.14159265358979323846264338327950288L;
+    std::vector<float2> h;
+    std::vector<FtCd> b, B, root;
+    try {
+      h.resize((size_t)(L + P));
+      b.assign((size_t)P, FtCd(0.0, 0.0));
+      B.resize((size_t)P);
+      root.resize((size_t)P);
+    } catch (const std::bad_alloc&) {
+      return DPZ_ERR_INTERNAL;
+    }
+    for (int64_t j = 0; j < L; ++j) {
+      const uint64_t ex = ((uint64_t)j * (uint64_t)j) % (uint64_t)(2 * L);
+      const long double th = pi * (long double)ex / (long double)L;
+      const long double cr = cosl(th), sr = sinl(th);
+      h[(size_t)j] = make_float2((float)cr, (float)-sr);
+      b[(size_t)j] = FtCd((double)cr, (double)sr);
+      if (j) b[(size_t)(P - j)] = b[(size_t)j];
+    }
+    for (int64_t e = 0; e < P; ++e) {
+      const long double th = 2.0L * pi * (long double)e / (long double)P;
+      root[(size_t)e] = FtCd((double)cosl(th), (double)-sinl(th));
+    }
+    ft_host_dft(b.data(), B.data(), P, 1, root.data(), 1);
+    for (int64_t i = 0; i < P; ++i)
+      h[(size_t)(L + i)] = make_float2((float)(B[(size_t)i].real() / (double)P),
+                                       (float)(B[(size_t)i].imag() / (double)P));
+    float2* d = nullptr;
+    DPZ_HIP_TRY(hipMalloc(&d, h.size() * sizeof(float2)));
+    if (hipMemcpy(d, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(d);
+      return DPZ_ERR_INTERNAL;
+    }
+    FtChirpTab t;
+    t.w = d;
+    t.bhat = d + L;
+    it = g_ft_chirp_tabs.emplace(key, t).first;
+  }
+  *out = it->second;
+  return DPZ_OK;
+}
+
+}  // namespace dpz
+
+// two rows of P complex per job, rows on 256 bytes: row r of job y at r * jobs * pitch + y * pitch
+static size_t ft_chirp_pitch(int64_t P) { return align256((size_t)P * sizeof(float2)); }
+
+extern "C" int64_t dpz_fft_chirp_length(int64_t n) {
+  const int64_t P = ft_chirp_len(n);
+  FtPlan pl;
+  return P > 0 && ft_make_plan(P, &pl) && pl.npass >= 1 ? P : 0;
+}
+
+extern "C" int64_t dpz_fft_chirp_nodes_workspace_bytes(int jobs, int64_t n) {
+  const int64_t P = dpz_fft_chirp_length(n);
+  if (jobs < 1 || P == 0) return -1;
+  return (int64_t)((size_t)jobs * ft_chirp_pitch(P) * 2 + 256);
+}
+
+static int ft_chirp_nodes(int jobs, const void* table, const void* host_table, int words,
+                          int64_t n, void* ws, size_t ws_bytes, hipStream_t st) {
+  if (jobs < 1 || !table || !host_table || (reinterpret_cast<uintptr_t>(table) & 7u))
+    return DPZ_ERR_ARG;
+  const int64_t P = dpz_fft_chirp_length(n);
+  FtPlan pl;
+  if (P == 0 || !ft_make_plan(P, &pl)) return DPZ_ERR_UNSUPPORTED;
+  int rc = ft_nodes_rows(jobs, host_table, words);
+  if (rc != DPZ_OK) return rc;
+  if (jobs > 65535) return DPZ_ERR_UNSUPPORTED;
+  if (!ws || (int64_t)ws_bytes < dpz_fft_chirp_nodes_workspace_bytes(jobs, n))
+    return DPZ_ERR_WORKSPACE;
+  FtTw twn, twp;
+  FtChirpTab ct;
+  if ((rc = ft_tables((uint32_t)n, &twn)) != DPZ_OK || (rc = ft_tables((uint32_t)P, &twp)) != DPZ_OK ||
+      (rc = ft_chirp_tables(n, P, &ct)) != DPZ_OK)
+    return rc;
+  const bool inverse = words == 2;
+  FtChirp c{};
+  c.tab = static_cast<const uint64_t*>(table);
+  c.pitch = ft_chirp_pitch(P);
+  c.w = ct.w;
+  c.bhat = ct.bhat;
+  c.L = n / 2;
+  c.P = P;
+  c.inverse = inverse ? 1 : 0;
+  c.scale = 1.0f / (float)n;
+  // a lands in row 0; DFT_P leaves row (npass & 1), the product stays there, the inverse DFT_P
+  // comes back to row 0 (ft_run's passes alternate and its last lands in `out`)
+  char* r0 = reinterpret_cast<char*>(ft_align(ws, 0));
+  char* r1 = r0 + (size_t)jobs * c.pitch;
+  float2* row0 = reinterpret_cast<float2*>(r0);
+  float2* mid = reinterpret_cast<float2*>((pl.npass & 1) ? r1 : r0);
+  float2* oth = reinterpret_cast<float2*>((pl.npass & 1) ? r0 : r1);
+  const dim3 gp(grid_for(P), (unsigned)jobs);
+  c.row = r0;
+  DPZ_TIMED(DPZ_KT_FFT, st, ft_chirp_pre_kernel<<<gp, 256, 0, st>>>(c, twn));
+  rc = ft_run(pl, twp, false, row0, nullptr, 0, mid, nullptr, 0, 1.0f, 0, oth, mid, st, nullptr,
+              nullptr, jobs, c.pitch);
+  if (rc != DPZ_OK) return rc;
+  c.row = reinterpret_cast<char*>(mid);
+  DPZ_TIMED(DPZ_KT_FFT, st, ft_chirp_mul_kernel<<<gp, 256, 0, st>>>(c));
+  float2* back_oth = reinterpret_cast<float2*>(r1);
+  rc = ft_run(pl, twp, true, mid, nullptr, 0, row0, nullptr, 0, 1.0f, 0, back_oth, row0, st,
+              nullptr, nullptr, jobs, c.pitch);
+  if (rc != DPZ_OK) return rc;
+  c.row = r0;
+  if (inverse) {
+    const dim3 g(grid_for(c.L), (unsigned)jobs);
+    DPZ_TIMED(DPZ_KT_FFT, st, ft_chirp_post_c2r_kernel<<<g, 256, 0, st>>>(c));
+  } else {
+    const dim3 g(grid_for(c.L / 2 + 1), (unsigned)jobs);
+    DPZ_TIMED(DPZ_KT_FFT, st, ft_chirp_post_r2c_kernel<<<g, 256, 0, st>>>(c, twn));
+  }
+  return DPZ_OK;
+}
+
+extern "C" int dpz_rfft_chirp_nodes(int jobs, const void* table, const void* host_table,
+                                    int64_t n, void* ws, size_t ws_bytes, dpz_stream_t stream) {
+  return ft_chirp_nodes(jobs, table, host_table, 4, n, ws, ws_bytes,
+                        static_cast<hipStream_t>(stream));
+}
+
+extern "C" int dpz_irfft_chirp_nodes(int jobs, const void* table, const void* host_table,
+                                     int64_t n, void* ws, size_t ws_bytes, dpz_stream_t stream) {
+  return ft_chirp_nodes(jobs, table, host_table, 2, n, ws, ws_bytes,
+                        static_cast<hipStream_t>(stream));
 }
 
 extern "C" int dpz_cplx_key(const float* change, float* acc, int acc_mode, int64_t m, float* key,

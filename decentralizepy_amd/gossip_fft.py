@@ -35,7 +35,11 @@ A ``step()`` is, whatever the node count and with no host synchronisation:
 Sizes without a native plan (``codec.fft_native(N)`` false: a prime factor of N / 2 above 4096,
 e.g. LeNet's 89,834 = 2 * 44,917) run the transforms of steps 1, 5 and 6 node after node through
 ``codec.rfft`` / ``codec.irfft`` (hipFFT) and the elementwise calls, as the per-node plugin does;
-the batched selection and fold still apply.  A batched hipFFT plan is not offered.
+the batched selection and fold still apply.  A batched hipFFT plan is not offered.  With
+``chirp=True`` such a size runs the three transform legs through ``dpz_rfft_chirp_nodes`` /
+``dpz_irfft_chirp_nodes`` on the same tables instead (the chirp-z algorithm: one launch set per
+leg again); ``batched`` says whether the transforms run as launch sets, ``native`` stays
+``codec.fft_native(N)``.  At a size with a native plan ``chirp`` changes nothing.
 
 Ties at the k-th key go to the lowest indices; finite models only.  The device FFT rounds
 differently from the reference's pocketfft, so parity with the reference is a tolerance parity
@@ -68,11 +72,13 @@ class FftRound(ShardedRound):
 
     def __init__(self, adj, x_init, alpha, rank=0, world=1, group=None, metadata_cap=1.0,
                  accumulation=False, accumulate_averaging_changes=False,
-                 change_based_selection=True, device=None, ops=None, **unknown):
+                 change_based_selection=True, device=None, ops=None, chirp=False, **unknown):
         if unknown:
             raise ValueError(
                 f"unknown arguments {sorted(unknown)}: FftRound offers neither compressed "
                 "payloads nor another exchange than the all-gather")
+        if not isinstance(chirp, bool):
+            raise ValueError(f"chirp={chirp!r}: True or False")
         if not change_based_selection:
             raise ValueError("change_based_selection=False (selection by |F(x)|) is not "
                              "offered: use the per-node plugin sharing.JWINS.FFT")
@@ -122,7 +128,8 @@ class FftRound(ShardedRound):
         self.send = torch.zeros(2 * self._half, **i32)
         self.recv = torch.zeros(world * 2 * self._half, **i32) if self.coll else None
         self.weights = [mh_weights(adj, i) for i in range(self.lo, self.hi)]
-        self.native = True
+        self.chirp = chirp
+        self.native = self.batched = True
         if self._hip and m:
             self._init_hip()
 
@@ -130,14 +137,18 @@ class FftRound(ShardedRound):
         from . import codec
         dev, m, M, N, k = self.device, self.m, self.M, self.N, self.k
         self.native = codec.fft_native(N)
+        self.batched = self.native or self.chirp
         xs, x0s = list(self.x), list(self.x0)
-        if self.native:
+        if self.batched:
             self._pre = codec.FftNodesTable(xs + xs, [None] * m + x0s,
                                             list(self.fx) + list(self.ch), False, dev)
             self._inv = codec.IfftNodesTable(self.ch, self.x, dev)
             self._post = codec.FftNodesTable(self.x, self.x0, self.acc, True, dev) \
                 if self.aac else None
-            self._fws = codec.fft_nodes_workspace(2 * m, N, dev)
+            if self.native:
+                self._fws = codec.fft_nodes_workspace(2 * m, N, dev)
+            else:  # the same tables through the chirp-z entry points
+                self._fws = codec.fft_chirp_nodes_workspace(2 * m, N, dev)
         else:
             self._fft_ws = codec.Workspace(dev)
             self._diff = torch.empty(N, dtype=torch.float32, device=dev)
@@ -193,6 +204,16 @@ class FftRound(ShardedRound):
         pairs, vals = self._pairs_vals(q)
         return pairs[0::2] // 2, torch.view_as_complex(vals.view(-1, 2))
 
+    def _rfft_nodes(self, table):
+        from . import codec
+        call = codec.rfft_nodes if self.native else codec.rfft_chirp_nodes
+        call(table, self.N, self._fws)
+
+    def _irfft_nodes(self, table):
+        from . import codec
+        call = codec.irfft_nodes if self.native else codec.irfft_chirp_nodes
+        call(table, self.N, self._fws)
+
     # ---- the legs of a round -----------------------------------------------------------------
     def encode(self):
         """F(x), F(x - x0) and the payload of every owned node; acc and the counter updated."""
@@ -201,8 +222,8 @@ class FftRound(ShardedRound):
             return
         if self._hip:
             from . import codec
-            if self.native:
-                codec.rfft_nodes(self._pre, self.N, self._fws)
+            if self.batched:
+                self._rfft_nodes(self._pre)
             else:
                 for j in range(m):
                     codec.elementwise(codec.DPZ_EW_SUB, self.x[j], self.x0[j], out=self._diff)
@@ -259,10 +280,10 @@ class FftRound(ShardedRound):
             return
         if self._hip:
             from . import codec
-            if self.native:
-                codec.irfft_nodes(self._inv, self.N, self._fws)
+            if self.batched:
+                self._irfft_nodes(self._inv)
                 if self.aac:
-                    codec.rfft_nodes(self._post, self.N, self._fws)
+                    self._rfft_nodes(self._post)
             else:
                 for j in range(self.m):
                     codec.irfft(self.ch[j], self.N, out=self.x[j], workspace=self._fft_ws)

@@ -1159,6 +1159,32 @@ int dpz_rfft_nodes(int jobs, const void* table, const void* host_table, int64_t 
                    size_t ws_bytes, dpz_stream_t stream);
 int dpz_irfft_nodes(int jobs, const void* table, const void* host_table, int64_t n, void* ws,
                     size_t ws_bytes, dpz_stream_t stream);
+/* ---- Chirp-z (Bluestein) real FFTs: the batched transforms at every even size -----------------
+ * dpz_rfft_chirp_nodes / dpz_irfft_chirp_nodes take dpz_rfft_nodes' / dpz_irfft_nodes' tables and
+ * mean the same transforms (the x0 subtraction one fp32 subtraction per element on load, the
+ * accumulating store one fp32 addition per component; x, x0 and coeffs only read), for EVERY even
+ * n in [4, 2^30] - sizes with a native plan included.  The complex DFT of length L = n / 2 runs as
+ * a cyclic convolution of the padded length P = dpz_fft_chirp_length(n), the smallest 7-smooth
+ * number >= 2 L - 1 (0 for an n the calls refuse): a = z . w (w_j = exp(-i pi j^2 / L), zero up to P), the
+ * native passes of DFT_P, the product with the cached table DFT_P(b) / P of the wrapped conjugate
+ * chirp (built in double on the host, rounded once), the inverse passes, then w_k and the even-n
+ * pairing; the inverse runs the chain from the c2r pairing with the conjugate chirp and 1 / n.
+ * The result agrees with the native kernels' to rounding, not bit for bit; a job's result does not
+ * depend on `jobs` or on its position.  2 npass(P) + 3 launches whatever `jobs` is (the job in the
+ * grid's second dimension), timed as "fft"; no host synchronisation.  The library allocates the
+ * per-(device, n) chirp tables (L + P complex) beside the twiddles.
+ * ws: dpz_fft_chirp_nodes_workspace_bytes(jobs, n) DEVICE bytes (-1 where refused): two rows of P
+ * complex per job.  Before anything is enqueued, as the native batched calls: DPZ_ERR_ARG for
+ * jobs < 1, a null or misaligned table, a null host table, a null x / out / coeffs, a row that is
+ * not 8-byte aligned, an accumulate word above 1; DPZ_ERR_UNSUPPORTED for an odd n, n < 4,
+ * n > 2^30 (before the rows are read) and jobs > 65535; DPZ_ERR_WORKSPACE for a null or short
+ * workspace.                                                                                      */
+int64_t dpz_fft_chirp_length(int64_t n);
+int64_t dpz_fft_chirp_nodes_workspace_bytes(int jobs, int64_t n);
+int dpz_rfft_chirp_nodes(int jobs, const void* table, const void* host_table, int64_t n, void* ws,
+                         size_t ws_bytes, dpz_stream_t stream);
+int dpz_irfft_chirp_nodes(int jobs, const void* table, const void* host_table, int64_t n, void* ws,
+                          size_t ws_bytes, dpz_stream_t stream);
 int64_t dpz_cplx_chunk_elems(void);
 size_t dpz_cplx_encode_workspace_bytes(int m, int64_t n);
 int dpz_cplx_encode_nodes(int m, const void* node_table, int64_t n, int64_t k, int acc_mode,

@@ -32,6 +32,13 @@ speed-up as the range [baseline min / engine max, baseline max / engine min]: a 
 contains 1 is no difference.  Prints one JSON line per shape.
 
     python tools/bench_fft_round.py [--shapes ref96,c4_96,c3_16] [--rounds 0] [--runs 3]
+
+``--chirp`` times another pair instead, at a size without a native plan (``--shapes lenet96``:
+``96_regular.edges`` x N = 89,834): ``FftRound(chirp=True)`` (reported as ``engine``: the chirp-z
+launch sets) against ``FftRound()`` (reported as ``baseline``: hipFFT node after node).  They are
+two algorithms for the same transforms, so what is checked is that their F(x) of the first round
+(from equal models) agree to 1e-5 of the largest coefficient; a selection whose k-th and
+(k + 1)-th keys lie closer than the rounding may differ, and the models then go their own way.
 """
 import argparse
 import json
@@ -54,7 +61,10 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 SHAPES = {"ref96": ("96_regular.edges", 90_112, 50),
           "c4_96": ("96_regular.edges", 11_000_000, 8),
           "c3_16": ("regular_16.edges", 25_000_000, 8),
-          "small16": ("regular_16.edges", 4_100, 20)}  # a quick check of the tool itself
+          "small16": ("regular_16.edges", 4_100, 20),  # a quick check of the tool itself
+          # --chirp only: the reference's CIFAR LeNet itself, a size without a native plan
+          "lenet96": ("96_regular.edges", 89_834, 50),
+          "chirp16": ("regular_16.edges", 8_198, 20)}
 
 
 class Baseline:
@@ -113,9 +123,9 @@ class Baseline:
 
 
 class Engine:
-    def __init__(self, adj, x_init, dev):
+    def __init__(self, adj, x_init, dev, chirp=False):
         self.eng = FftRound(adj, x_init, ALPHA, accumulation=True,
-                            accumulate_averaging_changes=True, device=dev)
+                            accumulate_averaging_changes=True, device=dev, chirp=chirp)
         self.x, self.x0 = self.eng.x, self.eng.x0
         self.acc, self.counter = self.eng.acc, self.eng.counter
 
@@ -156,6 +166,15 @@ def eq(a, b):
     return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
+def close_state(eng, base, m):
+    """--chirp: two algorithms for the same transforms.  F(x) of the first round comes from equal
+    models and agrees to rounding; where the k-th and the (k + 1)-th key of a node lie closer than
+    that rounding the selections differ, and the models follow their own course from there (one
+    tipped coefficient moves a model by about 1e-3), so nothing else is compared."""
+    f, g = eng.eng.fx, base.eng.fx
+    return float((f - g).abs().max()) <= 1e-5 * float(g.abs().max())
+
+
 def same_state(eng, base, m):
     ok = eq(eng.x, base.x) and eq(eng.x0, base.x0) and eq(eng.acc, base.acc)
     ok = ok and torch.equal(eng.counter, base.counter)
@@ -170,7 +189,7 @@ def run_shape(args, name, dev):
     rounds = args.rounds or rounds
     adj = read_edges(os.path.join(GOLDEN, edges))
     m = len(adj)
-    if not codec.fft_native(n):
+    if not codec.fft_native(n) and not args.chirp:
         raise SystemExit(f"{name}: N = {n} has no native plan")
     need = 26 * m * 4 * n + (1 << 30)  # both variants' rows, the workspace, the initial models
     free, _ = torch.cuda.mem_get_info(dev)
@@ -180,7 +199,10 @@ def run_shape(args, name, dev):
     gen = torch.Generator(device=dev).manual_seed(1)
     x0 = torch.randn(m, n, device=dev, generator=gen)
     noise = torch.randn(n, device=dev, generator=gen)  # the "training" step, rolled per node
-    variants = {"engine": Engine(adj, x0, dev), "baseline": Baseline(adj, x0, dev)}
+    if args.chirp:  # the chirp-z engine against the same engine without the keyword
+        variants = {"engine": Engine(adj, x0, dev, chirp=True), "baseline": Engine(adj, x0, dev)}
+    else:
+        variants = {"engine": Engine(adj, x0, dev), "baseline": Baseline(adj, x0, dev)}
     del x0
     eng, base = variants["engine"], variants["baseline"]
 
@@ -195,8 +217,11 @@ def run_shape(args, name, dev):
         for obj in variants.values():
             timed_round(obj)
         r += 1
-    torch.cuda.synchronize()
-    if not same_state(eng, base, m):
+        torch.cuda.synchronize()
+        if args.chirp and r == 1 and not close_state(eng, base, m):
+            raise SystemExit(f"{name}: the two engines' F(x) of the first round differ by more "
+                             "than rounding; nothing was timed")
+    if not args.chirp and not same_state(eng, base, m):
         raise SystemExit(f"{name}: the engine's and the baseline's states differ after two "
                          "rounds; nothing was timed")
     for _ in range(args.warmup):
@@ -218,11 +243,12 @@ def run_shape(args, name, dev):
             for leg, ts in legs[v].items():
                 runs[v].setdefault(leg, []).append(float(np.median(ts)))
     torch.cuda.synchronize()
-    same = same_state(eng, base, m)
+    same = None if args.chirp else same_state(eng, base, m)  # --chirp: checked after round one
     res = {"shape": name, "device": torch.cuda.get_device_name(0), "nodes": m, "n": n,
            "m_len": eng.eng.M, "k": eng.eng.k, "alpha": ALPHA, "rounds": rounds,
            "runs": args.runs, "warmup": args.warmup + 2, "total_rounds": r,
-           "equal_after_two_rounds": True, "results_equal": same}
+           "equal_after_two_rounds": True, "results_equal": same, "chirp": args.chirp,
+           "batched": eng.eng.batched, "native": eng.eng.native}
     for v in variants:
         res[v] = {leg: {"min_ms": round(min(t), 4), "max_ms": round(max(t), 4),
                         "runs_ms": [round(x, 4) for x in t]} for leg, t in runs[v].items()}
@@ -231,7 +257,7 @@ def run_shape(args, name, dev):
         res[f"{leg}_speedup"] = [round(b[leg]["min_ms"] / e[leg]["max_ms"], 2),
                                  round(b[leg]["max_ms"] / e[leg]["min_ms"], 2)]
     print(json.dumps(res), flush=True)
-    if not same:
+    if same is False:
         raise SystemExit(f"{name}: the engine's and the baseline's states differ")
 
 
@@ -241,6 +267,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=0, help="0: the shape's own count")
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--chirp", action="store_true",
+                    help="time FftRound(chirp=True) (as 'engine') against FftRound() (as "
+                         "'baseline'); their states agree to rounding, not bit for bit")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_fft_round needs a ROCm GPU; there is no CPU path")
