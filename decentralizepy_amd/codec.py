@@ -1522,6 +1522,20 @@ def choco_node_table(x, x_hat, rows):
     return _ptr_table((x, x_hat, rows, None), len(x), dev)
 
 
+def _encode_nodes(name, table, m, n, args, workspace):
+    """``dpz_<name>_encode_nodes`` on the m nodes of the device ``table``: size the workspace, grow
+    it where it is too small, call with ``args`` between n and the workspace, check; returns the
+    workspace."""
+    lib = _lib.lib()
+    need = int(getattr(lib, f"dpz_{name}_encode_workspace_bytes")(m, n))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=table.device)
+    rc = getattr(lib, f"dpz_{name}_encode_nodes")(m, _ptr(table), n, *args, _ptr(workspace),
+                                                   workspace.numel(), _stream(table.device))
+    check(rc, f"dpz_{name}_encode_nodes")
+    return workspace
+
+
 def choco_encode_nodes(table, n, k, cap, workspace=None):
     """Choco's ``_pre_step`` + ``serialized_model`` of every node of ``table``
     (``choco_node_table``): per node the threshold selection of ``topk_threshold(x - x_hat, k)``
@@ -1529,15 +1543,7 @@ def choco_encode_nodes(table, n, k, cap, workspace=None):
     written past ``cap`` when more are selected.  One launch set for all nodes, nothing read back.
     ``workspace``: a uint8 device tensor kept by the caller (allocated here when None); returned."""
     _require(table, torch.int64, "table")
-    m = table.shape[0]
-    need = int(_lib.lib().dpz_choco_encode_workspace_bytes(m, int(n)))
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=table.device)
-    rc = _lib.lib().dpz_choco_encode_nodes(m, _ptr(table), int(n), int(k), int(cap),
-                                           _ptr(workspace), workspace.numel(),
-                                           _stream(table.device))
-    check(rc, "dpz_choco_encode_nodes")
-    return workspace
+    return _encode_nodes("choco", table, table.shape[0], int(n), (int(k), int(cap)), workspace)
 
 
 class ChocoTable(_WordTable):
@@ -1623,14 +1629,7 @@ def stc_encode_nodes(table, n, k, workspace=None):
     ``r`` as it is.  One launch set for all nodes, nothing read back.  ``workspace``: a uint8
     device tensor kept by the caller (allocated here when None); returned."""
     _require(table, torch.int64, "table")
-    m = table.shape[0]
-    need = int(_lib.lib().dpz_stc_encode_workspace_bytes(m, int(n)))
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=table.device)
-    rc = _lib.lib().dpz_stc_encode_nodes(m, _ptr(table), int(n), int(k), _ptr(workspace),
-                                         workspace.numel(), _stream(table.device))
-    check(rc, "dpz_stc_encode_nodes")
-    return workspace
+    return _encode_nodes("stc", table, table.shape[0], int(n), (int(k),), workspace)
 
 
 class StcFoldTable(_WordTable):
@@ -1710,15 +1709,7 @@ def topkacc_encode_nodes(table, n, k, mode, workspace=None):
     ``acc[idx] = +0``.  One launch set for all nodes, nothing read back.  ``workspace``: a uint8
     device tensor kept by the caller (allocated here when None); returned."""
     _require(table, torch.int64, "table")
-    m = table.shape[0]
-    need = int(_lib.lib().dpz_topkacc_encode_workspace_bytes(m, int(n)))
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=table.device)
-    rc = _lib.lib().dpz_topkacc_encode_nodes(m, _ptr(table), int(n), int(k), int(mode),
-                                             _ptr(workspace), workspace.numel(),
-                                             _stream(table.device))
-    check(rc, "dpz_topkacc_encode_nodes")
-    return workspace
+    return _encode_nodes("topkacc", table, table.shape[0], int(n), (int(k), int(mode)), workspace)
 
 
 def topkacc_post_nodes(table, n):
@@ -1836,13 +1827,7 @@ def jwins_encode_nodes(table, n, workspace=None):
     if (table.host[:m, :3] == 0).any() or (table.host[:m, 4:6][part] == 0).any():
         raise ValueError("a node table with a null row: c, acc and vals_src of every node, "
                          "idx_out and val_out of every node with k >= 1")
-    need = int(_lib.lib().dpz_jwins_encode_workspace_bytes(m, n))
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=table.dev.device)
-    rc = _lib.lib().dpz_jwins_encode_nodes(m, _ptr(table.dev), n, _ptr(workspace),
-                                           workspace.numel(), _stream(table.dev.device))
-    check(rc, "dpz_jwins_encode_nodes")
-    return workspace
+    return _encode_nodes("jwins", table.dev, m, n, (), workspace)
 
 
 class FftNodesTable(_WordTable):
@@ -1999,14 +1984,7 @@ def cplx_encode_nodes(table, n, k, acc_mode=DPZ_ACC_NONE, workspace=None):
         raise ValueError("a misaligned row: complex rows and pair_out on 8 bytes, key and "
                          "counter on 4")
     _require(table.dev, torch.int64, "table")
-    need = int(_lib.lib().dpz_cplx_encode_workspace_bytes(m, n))
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=table.dev.device)
-    rc = _lib.lib().dpz_cplx_encode_nodes(m, _ptr(table.dev), n, k, int(acc_mode),
-                                          _ptr(workspace), workspace.numel(),
-                                          _stream(table.dev.device))
-    check(rc, "dpz_cplx_encode_nodes")
-    return workspace
+    return _encode_nodes("cplx", table.dev, m, n, (k, int(acc_mode)), workspace)
 
 
 class QuantInfo:

@@ -1,13 +1,11 @@
 // A Choco-SGD round of a rank's nodes (decentralizepy_amd/gossip_choco.py; reference
 // sharing/Choco.py:186-207 the threshold sparsification, :359-453 the round).
 //
-// dpz_choco_encode_nodes: `_pre_step` + `serialized_model` of m nodes, the node in the grid's
-// second dimension.  d = fl(x - x_hat) is formed on the fly in every pass and never stored; the
-// pass structure is that of the exact radix selection (dpz_topk_exact.hip) with a control block,
-// histograms and chunk counts per node: three histogram passes (10/11/10 bits of the key |d|)
-// each followed by a 1-block-per-node resolve give T, the k-th largest key; a count pass, a
-// 1-block-per-node scan and an ordered compaction write every i with key_i >= T and key_i != 0
-// (all ties, no exact zeros) in ascending order into the node's packed row.
+// dpz_choco_encode_nodes: `_pre_step` + `serialized_model` of m nodes: the selection of
+// dpz_select_nodes.h under ChocoPolicy.  d = fl(x - x_hat) is formed on the fly in every pass and
+// never stored (every pass reads x and x_hat alone); with T the k-th largest key |d|, every i with
+// key_i >= T and key_i != 0 (all ties, no exact zeros) goes in ascending order into the node's
+// packed row, and what is past the row's cap is reported by its status word, never written.
 //
 // dpz_choco_fold_nodes: `_averaging` of m receivers in one launch.  A block owns a column tile of
 // one receiver: the tile of s and of x_hat sits in LDS, each payload's first entry inside the tile
@@ -29,20 +27,15 @@
 #include <vector>
 
 #include "dpz_common.h"
-#include "dpz_topk.h"
+#include "dpz_select_nodes.h"
 
 namespace {
 
 using dpz::aligned16;
-using dpz::block_excl_scan;
-using dpz::block_excl_scan64;
-using dpz::key_of;
-using dpz::TopkCtrl;
 
 constexpr int64_t MAX_ELEMS = int64_t(1) << 31;
 constexpr int HEADER = 4;                 // int32 words in front of a row's idx / val slots
 constexpr int CHUNK = dpz::EX_CHUNK;      // elements per block of the count / compaction passes
-constexpr int HIST_BLOCKS = dpz::EX_HIST_BLOCKS;
 constexpr int TILE = 4096;                // fold: elements of one receiver a block owns
 constexpr int FOLD_THREADS = 256;
 constexpr int FOLD_GROUP = 8;             // payloads whose first entries a thread keeps in flight
@@ -56,29 +49,8 @@ struct ChocoNode {  // 4 64-bit words of the node table
 };
 static_assert(sizeof(ChocoNode) == 32, "4 64-bit words");
 
-struct EncWs {  // one node's share of the workspace
-  size_t ctrl, hist, bcnt, boff, total;
-  int64_t nblk;
-};
-
-EncWs enc_ws(int64_t n) {
-  EncWs L;
-  L.nblk = std::max<int64_t>(1, (n + CHUNK - 1) / CHUNK);
-  size_t o = 0;
-  L.ctrl = o; o += dpz::align256(sizeof(TopkCtrl));
-  L.hist = o; o += dpz::align256(4096 * 4);
-  L.bcnt = o; o += dpz::align256((size_t)L.nblk * 4);
-  L.boff = o; o += dpz::align256((size_t)L.nblk * 4);
-  L.total = o;
-  return L;
-}
-
-struct EncArgs {
+struct ChocoArgs {
   const ChocoNode* tab;
-  char* ws;
-  size_t per_node;
-  EncWs L;
-  int64_t n;
   uint32_t k;
   int64_t cap;
 };
@@ -86,8 +58,7 @@ struct EncArgs {
 // d = fl(x - x_hat) of the 4 elements from i0 (zeros past n); returns how many lie inside
 __device__ __forceinline__ int load_d4(const float* __restrict__ x, const float* __restrict__ xh,
                                        int64_t i0, int64_t n, bool vec, float d[4]) {
-  const int64_t rem = n - i0;
-  const int cnt = rem >= 4 ? 4 : (rem > 0 ? (int)rem : 0);
+  const int cnt = dpz::count4(i0, n);
   if (vec && cnt == 4) {
     const float4 a = *reinterpret_cast<const float4*>(x + i0);
     const float4 b = *reinterpret_cast<const float4*>(xh + i0);
@@ -99,166 +70,36 @@ __device__ __forceinline__ int load_d4(const float* __restrict__ x, const float*
   return cnt;
 }
 
-template <int P>
-__global__ void __launch_bounds__(256) choco_hist_kernel(const EncArgs a) {
-  constexpr int NB = (P == 1) ? 2048 : 1024;
-  constexpr int HOFF = (P == 0) ? 0 : (P == 1 ? 1024 : 3072);
-  __shared__ uint32_t h[NB];
-  for (int b = threadIdx.x; b < NB; b += 256) h[b] = 0;
-  __syncthreads();
-  const ChocoNode nd = a.tab[blockIdx.y];
-  char* ws = a.ws + (size_t)blockIdx.y * a.per_node;
-  const uint32_t pfx = (P == 0) ? 0u : reinterpret_cast<const TopkCtrl*>(ws + a.L.ctrl)->prefix;
-  uint32_t* ghist = reinterpret_cast<uint32_t*>(ws + a.L.hist) + HOFF;
-  const bool vec = aligned16(nd.x) && aligned16(nd.xh);
-  const int64_t ngroups = (a.n + 3) >> 2;
-  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < ngroups;
-       g += (int64_t)gridDim.x * 256) {
-    float d[4];
-    const int cnt = load_d4(nd.x, nd.xh, g * 4, a.n, vec, d);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (e < cnt) {
-        const uint32_t kk = key_of(d[e]);
-        if (P == 0) {
-          atomicAdd(&h[kk >> 21], 1u);
-        } else if (P == 1) {
-          if ((kk >> 21) == (pfx >> 21)) atomicAdd(&h[(kk >> 10) & 2047u], 1u);
-        } else {
-          if ((kk >> 10) == (pfx >> 10)) atomicAdd(&h[kk & 1023u], 1u);
-        }
-      }
-    }
+struct ChocoPolicy {  // dpz_select_nodes.h; no key row: every pass forms d from x and x_hat
+  using Node = ChocoNode;
+  using Args = ChocoArgs;
+  static constexpr bool kAllTies = true, kIdleNodes = false, kHeader = true;
+  static __device__ __forceinline__ uint32_t k(const Node, const Args a, int64_t) { return a.k; }
+  static __device__ __forceinline__ uint32_t slots(const Node, const Args a, int64_t) {
+    return (uint32_t)a.cap;
   }
-  __syncthreads();
-  for (int b = threadIdx.x; b < NB; b += 256) {
-    const uint32_t v = h[b];
-    if (v) atomicAdd(&ghist[b], v);
+  template <bool FIRST>
+  static __device__ __forceinline__ bool vec(const Node nd, const Args) {
+    return aligned16(nd.x) && aligned16(nd.xh);
   }
-}
-
-// One block of 1024 threads per node: the digit that holds the krem-th largest key.
-template <int P>
-__global__ void __launch_bounds__(1024) choco_resolve_kernel(const EncArgs a) {
-  constexpr int NB = (P == 1) ? 2048 : 1024;
-  constexpr int HOFF = (P == 0) ? 0 : (P == 1 ? 1024 : 3072);
-  constexpr int SH = (P == 0) ? 21 : (P == 1 ? 10 : 0);
-  constexpr int PER = NB / 1024;
-  __shared__ uint32_t wsum[16];
-  char* ws = a.ws + (size_t)blockIdx.x * a.per_node;
-  TopkCtrl* ctrl = reinterpret_cast<TopkCtrl*>(ws + a.L.ctrl);
-  const uint32_t* ghist = reinterpret_cast<const uint32_t*>(ws + a.L.hist) + HOFF;
-  const uint32_t krem = (P == 0) ? a.k : ctrl->krem;
-  const uint32_t pfx = (P == 0) ? 0u : ctrl->prefix;
-  __syncthreads();  // every thread has read ctrl before one of them rewrites it
-  uint32_t hv[PER];
-  uint32_t local = 0;
-#pragma unroll
-  for (int q = 0; q < PER; ++q) {  // descending bins
-    hv[q] = ghist[NB - 1 - (threadIdx.x * PER + q)];
-    local += hv[q];
+  template <bool FIRST>
+  static __device__ __forceinline__ int load4(const Node nd, const Args, int64_t i0, int64_t n,
+                                              bool vec, float d[4]) {
+    return load_d4(nd.x, nd.xh, i0, n, vec, d);
   }
-  uint32_t tot;
-  uint32_t before = block_excl_scan(local, wsum, &tot);
-#pragma unroll
-  for (int q = 0; q < PER; ++q) {
-    if (before < krem && krem <= before + hv[q]) {
-      const uint32_t d = NB - 1 - (threadIdx.x * PER + q);
-      ctrl->prefix = pfx | (d << SH);
-      ctrl->krem = krem - before;
-    }
-    before += hv[q];
-  }
-}
-
-// selected: key >= T, and not a zero key (T == 0: fewer than k nonzeros, the zeros stay home)
-__device__ __forceinline__ bool choco_sel(uint32_t key, uint32_t T) {
-  return key >= (T ? T : 1u);
-}
-
-__global__ void __launch_bounds__(256) choco_count_kernel(const EncArgs a) {
-  __shared__ uint32_t wsum[16];
-  const ChocoNode nd = a.tab[blockIdx.y];
-  char* ws = a.ws + (size_t)blockIdx.y * a.per_node;
-  const uint32_t T = reinterpret_cast<const TopkCtrl*>(ws + a.L.ctrl)->prefix;
-  const bool vec = aligned16(nd.x) && aligned16(nd.xh);
-  const int64_t lo = (int64_t)blockIdx.x * CHUNK;
-  uint32_t c = 0;
-  for (int r = 0; r < CHUNK / 1024; ++r) {
-    const int64_t i0 = lo + r * 1024 + threadIdx.x * 4;
-    if (i0 >= a.n) break;
-    float d[4];
-    const int cnt = load_d4(nd.x, nd.xh, i0, a.n, vec, d);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) c += (e < cnt && choco_sel(key_of(d[e]), T)) ? 1u : 0u;
-  }
-  uint32_t tot;
-  block_excl_scan(c, wsum, &tot);
-  if (threadIdx.x == 0) reinterpret_cast<uint32_t*>(ws + a.L.bcnt)[blockIdx.x] = tot;
-}
-
-// One block of 1024 threads per node: every chunk's output offset, and the row's header.
-__global__ void __launch_bounds__(1024) choco_scan_kernel(const EncArgs a) {
-  __shared__ uint64_t wsum[16];
-  const ChocoNode nd = a.tab[blockIdx.x];
-  char* ws = a.ws + (size_t)blockIdx.x * a.per_node;
-  const uint32_t* bcnt = reinterpret_cast<const uint32_t*>(ws + a.L.bcnt);
-  uint32_t* boff = reinterpret_cast<uint32_t*>(ws + a.L.boff);
-  uint64_t carry = 0;
-  for (int64_t base = 0; base < a.L.nblk; base += 1024) {
-    const int64_t b = base + threadIdx.x;
-    const uint64_t c = b < a.L.nblk ? bcnt[b] : 0;
-    uint64_t ts;
-    const uint64_t off = block_excl_scan64(c, wsum, &ts) + carry;
-    if (b < a.L.nblk) boff[b] = (uint32_t)off;
-    carry += ts;
-  }
-  if (threadIdx.x == 0) {  // count < 2^31: the int64's high word is 0
-    nd.row[0] = (int32_t)carry;
+  // count < 2^31: the int64's high word is 0; an overflow is reported by the status word
+  static __device__ __forceinline__ void header(const Node nd, const Args a, uint64_t count) {
+    nd.row[0] = (int32_t)count;
     nd.row[1] = 0;
-    nd.row[2] = carry > (uint64_t)a.cap ? 1 : 0;
+    nd.row[2] = count > (uint64_t)a.cap ? 1 : 0;
     nd.row[3] = 0;
   }
-}
-
-__global__ void __launch_bounds__(256) choco_write_kernel(const EncArgs a) {
-  __shared__ uint32_t wsum[16];
-  const ChocoNode nd = a.tab[blockIdx.y];
-  char* ws = a.ws + (size_t)blockIdx.y * a.per_node;
-  const uint32_t T = reinterpret_cast<const TopkCtrl*>(ws + a.L.ctrl)->prefix;
-  const uint32_t off0 = reinterpret_cast<const uint32_t*>(ws + a.L.boff)[blockIdx.x];
-  const bool vec = aligned16(nd.x) && aligned16(nd.xh);
-  int32_t* idx_out = nd.row + HEADER;
-  float* val_out = reinterpret_cast<float*>(nd.row + HEADER + a.cap);
-  const int64_t lo = (int64_t)blockIdx.x * CHUNK;
-  uint32_t run = 0;
-  for (int r = 0; r < CHUNK / 1024; ++r) {
-    if (lo + r * 1024 >= a.n) break;  // uniform
-    const int64_t i0 = lo + r * 1024 + threadIdx.x * 4;
-    float d[4];
-    const int cnt = load_d4(nd.x, nd.xh, i0, a.n, vec, d);
-    bool sel[4];
-    uint32_t c = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      sel[e] = e < cnt && choco_sel(key_of(d[e]), T);
-      c += sel[e] ? 1u : 0u;
-    }
-    uint32_t tot;
-    uint64_t pos = (uint64_t)off0 + run + block_excl_scan(c, wsum, &tot);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (sel[e]) {
-        if (pos < (uint64_t)a.cap) {  // an overflow is reported by the status word, never written
-          idx_out[pos] = (int32_t)(i0 + e);
-          val_out[pos] = d[e];
-        }
-        ++pos;
-      }
-    }
-    run += tot;
+  static __device__ __forceinline__ void store(const Node nd, const Args a, uint32_t pos,
+                                               int64_t i, float d) {
+    nd.row[HEADER + pos] = (int32_t)i;
+    reinterpret_cast<float*>(nd.row + HEADER + a.cap)[pos] = d;
   }
-}
+};
 
 // ---- fold ---------------------------------------------------------------------------------------
 struct ChocoRecv {  // 6 64-bit words
@@ -469,7 +310,7 @@ extern "C" int64_t dpz_choco_tile_elems(void) { return TILE; }
 
 extern "C" size_t dpz_choco_encode_workspace_bytes(int m, int64_t n) {
   if (m < 1 || n < 1) return 0;
-  return (size_t)m * enc_ws(n).total;
+  return (size_t)m * dpz::node_ws(n).total;
 }
 
 extern "C" int dpz_choco_encode_nodes(int m, const void* node_table, int64_t n, int64_t k,
@@ -478,30 +319,11 @@ extern "C" int dpz_choco_encode_nodes(int m, const void* node_table, int64_t n, 
   if (m < 1 || n < 1 || k < 1 || k > n || cap < 1 || !node_table || !ws) return DPZ_ERR_ARG;
   if (n >= MAX_ELEMS || cap >= MAX_ELEMS || m > 65535) return DPZ_ERR_UNSUPPORTED;
   if (ws_bytes < dpz_choco_encode_workspace_bytes(m, n)) return DPZ_ERR_WORKSPACE;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  EncArgs a;
+  ChocoArgs a;
   a.tab = static_cast<const ChocoNode*>(node_table);
-  a.ws = static_cast<char*>(ws);
-  a.L = enc_ws(n);
-  a.per_node = a.L.total;
-  a.n = n;
   a.k = (uint32_t)k;
   a.cap = cap;
-  // every node's control block and histograms (the chunk arrays are written before they are read)
-  DPZ_HIP_TRY(hipMemsetAsync(ws, 0, (size_t)m * a.per_node, st));
-  const int64_t groups = (n + 3) / 4;
-  const unsigned hb = (unsigned)std::min<int64_t>(HIST_BLOCKS, (groups + 255) / 256);
-  const dim3 hgrid(hb, (unsigned)m), cgrid((unsigned)a.L.nblk, (unsigned)m);
-  DPZ_TIMED(DPZ_KT_EXACT_HIST, st, choco_hist_kernel<0><<<hgrid, 256, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_RESOLVE, st, choco_resolve_kernel<0><<<m, 1024, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_HIST, st, choco_hist_kernel<1><<<hgrid, 256, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_RESOLVE, st, choco_resolve_kernel<1><<<m, 1024, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_HIST, st, choco_hist_kernel<2><<<hgrid, 256, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_RESOLVE, st, choco_resolve_kernel<2><<<m, 1024, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_COUNT, st, choco_count_kernel<<<cgrid, 256, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_SCAN, st, choco_scan_kernel<<<m, 1024, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_WRITE, st, choco_write_kernel<<<cgrid, 256, 0, st>>>(a));
-  return DPZ_OK;
+  return dpz::select_nodes<ChocoPolicy>(m, a, n, ws, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int dpz_choco_fold_nodes(int m, const void* fold_table, const void* host_table,

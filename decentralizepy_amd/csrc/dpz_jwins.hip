@@ -2,20 +2,16 @@
 // sharing/JWINS/Wavelet.py:142-231 `apply_wavelet` + `serialized_model` over
 // sharing/PartialModel.py:305-331 `_pre_step` with accumulate_averaging_changes).
 //
-// dpz_jwins_encode_nodes: the exact selection of m nodes, the node in the grid's second
-// dimension, each node with ITS OWN k (JWINS draws alpha per node and round) and with the values
-// taken from a row other than the one the key is formed from.  The pass structure is that of
-// dpz_topkacc_encode_nodes (a self-contained sibling: a control block, histograms and chunk
-// counts per node; one memset and nine launches whatever m is).  Per node, c = W(x - x0):
+// dpz_jwins_encode_nodes: the exact selection of m nodes (dpz_select_nodes.h) under JwPolicy,
+// each node with ITS OWN k (JWINS draws alpha per node and round) and with the values taken from a
+// row other than the one the key is formed from.  Per node, c = W(x - x0):
 //   1 <= k <= n   the first histogram pass forms the key vector fl(c + acc) once (8 n bytes read)
 //                 and stores it IN PLACE into the c row (4 n written): the round has no further
 //                 use for W(x - x0), and the fold overwrites the row afterwards.  Every later pass
-//                 reads the c row alone (4 n).  Three histogram passes (10/11/10 bits of |key|),
-//                 each followed by a 1-block-per-node resolve, give T, the k-th largest key, and
-//                 the number of ties at T to take; a count pass, a 1-block-per-node scan and the
-//                 ordered compaction write idx ascending / val = vals_src[idx] into the node's
-//                 slots, counter[idx] += 1 (a plain store: the element has one owner) and +0 into
-//                 acc[idx].  Exactly k entries; ties at T go to the lowest indices.
+//                 reads the c row alone (4 n).  The compaction writes idx ascending /
+//                 val = vals_src[idx] into the node's slots, counter[idx] += 1 (a plain store: the
+//                 element has one owner) and +0 into acc[idx].  Exactly k entries; ties at the
+//                 k-th largest key go to the lowest indices.
 //   k == 0        a full share (Wavelet.py:185-192): the first pass stores +0 to all of acc and,
 //                 if val_out is set, copies vals_src to val_out (n floats).  No other pass
 //                 touches the node: its blocks leave at once.
@@ -24,19 +20,16 @@
 #include <algorithm>
 
 #include "dpz_common.h"
-#include "dpz_topk.h"
+#include "dpz_select_nodes.h"
 
 namespace {
 
 using dpz::aligned16;
-using dpz::block_excl_scan;
-using dpz::block_excl_scan64;
-using dpz::key_of;
-using dpz::TopkCtrl;
+using dpz::count4;
+using dpz::load_c4;
 
 constexpr int64_t MAX_ELEMS = int64_t(1) << 31;
 constexpr int CHUNK = dpz::EX_CHUNK;      // elements per block of the count / compaction passes
-constexpr int HIST_BLOCKS = dpz::EX_HIST_BLOCKS;
 
 struct JwNode {  // 8 64-bit words of the node table
   float* c;            // W(x - x0); the key vector after the first pass
@@ -50,60 +43,18 @@ struct JwNode {  // 8 64-bit words of the node table
 };
 static_assert(sizeof(JwNode) == 64, "8 64-bit words");
 
-struct EncWs {  // one node's share of the workspace
-  size_t ctrl, hist, bgt, beq, boff, beqb, total;
-  int64_t nblk;
-};
-
-EncWs enc_ws(int64_t n) {
-  EncWs L;
-  L.nblk = std::max<int64_t>(1, (n + CHUNK - 1) / CHUNK);
-  size_t o = 0;
-  L.ctrl = o; o += dpz::align256(sizeof(TopkCtrl));
-  L.hist = o; o += dpz::align256(4096 * 4);
-  L.bgt = o; o += dpz::align256((size_t)L.nblk * 4);
-  L.beq = o; o += dpz::align256((size_t)L.nblk * 4);
-  L.boff = o; o += dpz::align256((size_t)L.nblk * 4);
-  L.beqb = o; o += dpz::align256((size_t)L.nblk * 4);
-  L.total = o;
-  return L;
-}
-
-struct EncArgs {
+struct JwArgs {
   const JwNode* tab;
-  char* ws;
-  size_t per_node;
-  EncWs L;
-  int64_t n;
 };
 
 // the node's k; a k past n (the caller's error, refused by the Python wrapper) selects all n, so
 // that no pass writes outside the node's rows
-__device__ __forceinline__ uint32_t node_k(const JwNode& nd, int64_t n) {
+__device__ __forceinline__ uint32_t node_k(const JwNode nd, int64_t n) {
   return nd.k > (uint64_t)n ? (uint32_t)n : (uint32_t)nd.k;
 }
 
-__device__ __forceinline__ int count4(int64_t i0, int64_t n) {
-  const int64_t rem = n - i0;
-  return rem >= 4 ? 4 : (rem > 0 ? (int)rem : 0);
-}
-
-// c = the key row's 4 elements from i0 (zeros past n); returns how many lie inside
-__device__ __forceinline__ int load_c4(const float* __restrict__ r, int64_t i0, int64_t n,
-                                       bool vec, float c[4]) {
-  const int cnt = count4(i0, n);
-  if (vec && cnt == 4) {
-    const float4 q = *reinterpret_cast<const float4*>(r + i0);
-    c[0] = q.x, c[1] = q.y, c[2] = q.z, c[3] = q.w;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) c[e] = e < cnt ? r[i0 + e] : 0.0f;
-  }
-  return cnt;
-}
-
 // key = fl(c + acc) of the 4 elements from i0, stored in place into the c row
-__device__ __forceinline__ int form_c4(const JwNode& nd, int64_t i0, int64_t n, bool vec,
+__device__ __forceinline__ int form_c4(const JwNode nd, int64_t i0, int64_t n, bool vec,
                                        float c[4]) {
   const int cnt = count4(i0, n);
   if (vec && cnt == 4) {
@@ -125,7 +76,7 @@ __device__ __forceinline__ int form_c4(const JwNode& nd, int64_t i0, int64_t n, 
 }
 
 // a full share: acc = +0 everywhere, val_out = vals_src when set
-__device__ __forceinline__ void full_share(const JwNode& nd, int64_t n) {
+__device__ __forceinline__ void full_share(const JwNode nd, int64_t n) {
   const bool vz = aligned16(nd.acc);
   const bool vc = nd.val_out && aligned16(nd.vals) && aligned16(nd.val_out);
   const int64_t ngroups = (n + 3) >> 2;
@@ -149,209 +100,38 @@ __device__ __forceinline__ void full_share(const JwNode& nd, int64_t n) {
   }
 }
 
-template <int P>
-__global__ void __launch_bounds__(256) jwins_hist_kernel(const EncArgs a) {
-  constexpr int NB = (P == 1) ? 2048 : 1024;
-  constexpr int HOFF = (P == 0) ? 0 : (P == 1 ? 1024 : 3072);
-  __shared__ uint32_t h[NB];
-  const JwNode nd = a.tab[blockIdx.y];
-  if (nd.k == 0) {  // uniform over the block
-    if (P == 0) full_share(nd, a.n);
-    return;
+struct JwPolicy {  // dpz_select_nodes.h; the key row is c
+  using Node = JwNode;
+  using Args = JwArgs;
+  static constexpr bool kAllTies = false, kIdleNodes = true, kHeader = false;
+  static __device__ __forceinline__ bool idle(const Node nd) { return nd.k == 0; }
+  static __device__ __forceinline__ void idle_share(const Node nd, int64_t n) {
+    full_share(nd, n);
   }
-  for (int b = threadIdx.x; b < NB; b += 256) h[b] = 0;
-  __syncthreads();
-  char* ws = a.ws + (size_t)blockIdx.y * a.per_node;
-  const uint32_t pfx = (P == 0) ? 0u : reinterpret_cast<const TopkCtrl*>(ws + a.L.ctrl)->prefix;
-  uint32_t* ghist = reinterpret_cast<uint32_t*>(ws + a.L.hist) + HOFF;
-  const bool vec = aligned16(nd.c) && (P != 0 || aligned16(nd.acc));
-  const int64_t ngroups = (a.n + 3) >> 2;
-  // every group of 4 belongs to exactly one thread of the grid: the key is formed and stored once
-  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < ngroups;
-       g += (int64_t)gridDim.x * 256) {
-    float c[4];
-    const int cnt = (P == 0) ? form_c4(nd, g * 4, a.n, vec, c) : load_c4(nd.c, g * 4, a.n, vec, c);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (e < cnt) {
-        const uint32_t kk = key_of(c[e]);
-        if (P == 0) {
-          atomicAdd(&h[kk >> 21], 1u);
-        } else if (P == 1) {
-          if ((kk >> 21) == (pfx >> 21)) atomicAdd(&h[(kk >> 10) & 2047u], 1u);
-        } else {
-          if ((kk >> 10) == (pfx >> 10)) atomicAdd(&h[kk & 1023u], 1u);
-        }
-      }
-    }
+  static __device__ __forceinline__ uint32_t k(const Node nd, const Args, int64_t n) {
+    return node_k(nd, n);
   }
-  __syncthreads();
-  for (int b = threadIdx.x; b < NB; b += 256) {
-    const uint32_t v = h[b];
-    if (v) atomicAdd(&ghist[b], v);
+  static __device__ __forceinline__ uint32_t slots(const Node nd, const Args, int64_t n) {
+    return node_k(nd, n);
   }
-}
-
-// One block of 1024 threads per node: the digit that holds the krem-th largest key.
-template <int P>
-__global__ void __launch_bounds__(1024) jwins_resolve_kernel(const EncArgs a) {
-  constexpr int NB = (P == 1) ? 2048 : 1024;
-  constexpr int HOFF = (P == 0) ? 0 : (P == 1 ? 1024 : 3072);
-  constexpr int SH = (P == 0) ? 21 : (P == 1 ? 10 : 0);
-  constexpr int PER = NB / 1024;
-  __shared__ uint32_t wsum[16];
-  const JwNode nd = a.tab[blockIdx.x];
-  if (nd.k == 0) return;  // uniform over the block
-  char* ws = a.ws + (size_t)blockIdx.x * a.per_node;
-  TopkCtrl* ctrl = reinterpret_cast<TopkCtrl*>(ws + a.L.ctrl);
-  const uint32_t* ghist = reinterpret_cast<const uint32_t*>(ws + a.L.hist) + HOFF;
-  const uint32_t krem = (P == 0) ? node_k(nd, a.n) : ctrl->krem;
-  const uint32_t pfx = (P == 0) ? 0u : ctrl->prefix;
-  __syncthreads();  // every thread has read ctrl before one of them rewrites it
-  uint32_t hv[PER];
-  uint32_t local = 0;
-#pragma unroll
-  for (int q = 0; q < PER; ++q) {  // descending bins
-    hv[q] = ghist[NB - 1 - (threadIdx.x * PER + q)];
-    local += hv[q];
+  template <bool FIRST>
+  static __device__ __forceinline__ bool vec(const Node nd, const Args) {
+    return aligned16(nd.c) && (!FIRST || aligned16(nd.acc));
   }
-  uint32_t tot;
-  uint32_t before = block_excl_scan(local, wsum, &tot);
-#pragma unroll
-  for (int q = 0; q < PER; ++q) {
-    if (before < krem && krem <= before + hv[q]) {
-      const uint32_t d = NB - 1 - (threadIdx.x * PER + q);
-      ctrl->prefix = pfx | (d << SH);
-      ctrl->krem = krem - before;  // after the last pass: the ties at T to take
-    }
-    before += hv[q];
+  template <bool FIRST>
+  static __device__ __forceinline__ int load4(const Node nd, const Args, int64_t i0, int64_t n,
+                                              bool vec, float c[4]) {
+    return FIRST ? form_c4(nd, i0, n, vec, c) : load_c4(nd.c, i0, n, vec, c);
   }
-}
-
-// key > T in the low half, key == T in the high half: a chunk holds 8192 < 2^16 elements
-__device__ __forceinline__ uint32_t count_gt_eq(const float c[4], int cnt, uint32_t T) {
-  uint32_t v = 0;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    if (e < cnt) {
-      const uint32_t kk = key_of(c[e]);
-      v += (kk > T ? 1u : 0u) + (kk == T ? 0x10000u : 0u);
-    }
+  // this thread owns element i: plain stores
+  static __device__ __forceinline__ void store(const Node nd, const Args, uint32_t pos,
+                                               int64_t i, float) {
+    nd.idx_out[pos] = (int32_t)i;
+    nd.val_out[pos] = nd.vals[i];
+    if (nd.counter) nd.counter[i] = nd.counter[i] + 1;
+    nd.acc[i] = 0.0f;  // the rewind: what was sent is no longer owed
   }
-  return v;
-}
-static_assert(CHUNK < 0x10000, "two 16-bit counts per chunk");
-
-__global__ void __launch_bounds__(256) jwins_count_kernel(const EncArgs a) {
-  __shared__ uint32_t wsum[16];
-  const JwNode nd = a.tab[blockIdx.y];
-  if (nd.k == 0) return;  // uniform over the block
-  char* ws = a.ws + (size_t)blockIdx.y * a.per_node;
-  const uint32_t T = reinterpret_cast<const TopkCtrl*>(ws + a.L.ctrl)->prefix;
-  const bool vec = aligned16(nd.c);
-  const int64_t lo = (int64_t)blockIdx.x * CHUNK;
-  uint32_t v = 0;
-  for (int r = 0; r < CHUNK / 1024; ++r) {
-    const int64_t i0 = lo + r * 1024 + threadIdx.x * 4;
-    if (i0 >= a.n) break;
-    float c[4];
-    const int cnt = load_c4(nd.c, i0, a.n, vec, c);
-    v += count_gt_eq(c, cnt, T);
-  }
-  uint32_t tot;
-  block_excl_scan(v, wsum, &tot);
-  if (threadIdx.x == 0) {
-    reinterpret_cast<uint32_t*>(ws + a.L.bgt)[blockIdx.x] = tot & 0xFFFFu;
-    reinterpret_cast<uint32_t*>(ws + a.L.beq)[blockIdx.x] = tot >> 16;
-  }
-}
-
-// One block of 1024 threads per node: every chunk's output offset and the ties before it (its
-// share of the allotment follows: ties go to the lowest indices).
-__global__ void __launch_bounds__(1024) jwins_scan_kernel(const EncArgs a) {
-  __shared__ uint64_t wsum[16];
-  const JwNode nd = a.tab[blockIdx.x];
-  if (nd.k == 0) return;  // uniform over the block
-  char* ws = a.ws + (size_t)blockIdx.x * a.per_node;
-  const uint64_t ties = reinterpret_cast<const TopkCtrl*>(ws + a.L.ctrl)->krem;
-  const uint32_t* bgt = reinterpret_cast<const uint32_t*>(ws + a.L.bgt);
-  const uint32_t* beq = reinterpret_cast<const uint32_t*>(ws + a.L.beq);
-  uint32_t* boff = reinterpret_cast<uint32_t*>(ws + a.L.boff);
-  uint32_t* beqb = reinterpret_cast<uint32_t*>(ws + a.L.beqb);
-  uint64_t carry_eq = 0, carry_off = 0;
-  for (int64_t base = 0; base < a.L.nblk; base += 1024) {
-    const int64_t b = base + threadIdx.x;
-    const uint64_t gt = b < a.L.nblk ? bgt[b] : 0;
-    const uint64_t eq = b < a.L.nblk ? beq[b] : 0;
-    uint64_t te;
-    const uint64_t eqb = block_excl_scan64(eq, wsum, &te) + carry_eq;
-    uint64_t take = 0;
-    if (ties > eqb) take = (ties - eqb) < eq ? (ties - eqb) : eq;
-    uint64_t ts;
-    const uint64_t off = block_excl_scan64(gt + take, wsum, &ts) + carry_off;
-    if (b < a.L.nblk) {
-      boff[b] = (uint32_t)off;
-      beqb[b] = (uint32_t)(eqb < ties ? eqb : ties);
-    }
-    carry_eq += te;
-    carry_off += ts;
-  }
-}
-
-__global__ void __launch_bounds__(256) jwins_write_kernel(const EncArgs a) {
-  __shared__ uint32_t wsum[16];
-  const JwNode nd = a.tab[blockIdx.y];
-  if (nd.k == 0) return;  // uniform over the block
-  const uint32_t k = node_k(nd, a.n);
-  char* ws = a.ws + (size_t)blockIdx.y * a.per_node;
-  const TopkCtrl* ctrl = reinterpret_cast<const TopkCtrl*>(ws + a.L.ctrl);
-  const uint32_t T = ctrl->prefix;
-  const uint32_t ties = ctrl->krem;
-  const uint32_t off0 = reinterpret_cast<const uint32_t*>(ws + a.L.boff)[blockIdx.x];
-  const uint32_t eqb = reinterpret_cast<const uint32_t*>(ws + a.L.beqb)[blockIdx.x];
-  const uint32_t quota = ties > eqb ? ties - eqb : 0u;
-  const bool vec = aligned16(nd.c);
-  const int64_t lo = (int64_t)blockIdx.x * CHUNK;
-  uint32_t gt_run = 0, eq_run = 0;
-  for (int r = 0; r < CHUNK / 1024; ++r) {
-    if (lo + r * 1024 >= a.n) break;  // uniform
-    const int64_t i0 = lo + r * 1024 + threadIdx.x * 4;
-    float c[4];
-    const int cnt = load_c4(nd.c, i0, a.n, vec, c);
-    uint32_t tot;
-    const uint32_t ex = block_excl_scan(count_gt_eq(c, cnt, T), wsum, &tot);
-    uint32_t g = gt_run + (ex & 0xFFFFu);
-    uint32_t q = eq_run + (ex >> 16);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (e < cnt) {
-        const uint32_t kk = key_of(c[e]);
-        bool sel = false;
-        uint32_t pos = 0;
-        if (kk > T) {
-          sel = true;
-          pos = off0 + g + (q < quota ? q : quota);
-          ++g;
-        } else if (kk == T) {
-          if (q < quota) {
-            sel = true;
-            pos = off0 + g + q;
-          }
-          ++q;
-        }
-        if (sel && pos < k) {  // pos < k always; the slot is never written past
-          const int64_t i = i0 + e;  // this thread owns element i: plain stores
-          nd.idx_out[pos] = (int32_t)i;
-          nd.val_out[pos] = nd.vals[i];
-          if (nd.counter) nd.counter[i] = nd.counter[i] + 1;
-          nd.acc[i] = 0.0f;  // the rewind: what was sent is no longer owed
-        }
-      }
-    }
-    gt_run += tot & 0xFFFFu;
-    eq_run += tot >> 16;
-  }
-}
+};
 
 }  // namespace
 
@@ -359,7 +139,7 @@ extern "C" int64_t dpz_jwins_chunk_elems(void) { return CHUNK; }
 
 extern "C" size_t dpz_jwins_encode_workspace_bytes(int m, int64_t n) {
   if (m < 1 || n < 1) return 0;
-  return (size_t)m * enc_ws(n).total;
+  return (size_t)m * dpz::node_ws(n).total;
 }
 
 extern "C" int dpz_jwins_encode_nodes(int m, const void* node_table, int64_t n, void* ws,
@@ -370,26 +150,7 @@ extern "C" int dpz_jwins_encode_nodes(int m, const void* node_table, int64_t n, 
     return DPZ_ERR_ARG;
   if (ws_bytes < dpz_jwins_encode_workspace_bytes(m, n)) return DPZ_ERR_ARG;
   if (m > 65535) return DPZ_ERR_UNSUPPORTED;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  EncArgs a;
+  JwArgs a;
   a.tab = static_cast<const JwNode*>(node_table);
-  a.ws = static_cast<char*>(ws);
-  a.L = enc_ws(n);
-  a.per_node = a.L.total;
-  a.n = n;
-  // every node's control block and histograms (the chunk arrays are written before they are read)
-  DPZ_HIP_TRY(hipMemsetAsync(ws, 0, (size_t)m * a.per_node, st));
-  const int64_t groups = (n + 3) / 4;
-  const unsigned hb = (unsigned)std::min<int64_t>(HIST_BLOCKS, (groups + 255) / 256);
-  const dim3 hgrid(hb, (unsigned)m), cgrid((unsigned)a.L.nblk, (unsigned)m);
-  DPZ_TIMED(DPZ_KT_EXACT_HIST, st, jwins_hist_kernel<0><<<hgrid, 256, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_RESOLVE, st, jwins_resolve_kernel<0><<<m, 1024, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_HIST, st, jwins_hist_kernel<1><<<hgrid, 256, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_RESOLVE, st, jwins_resolve_kernel<1><<<m, 1024, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_HIST, st, jwins_hist_kernel<2><<<hgrid, 256, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_RESOLVE, st, jwins_resolve_kernel<2><<<m, 1024, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_COUNT, st, jwins_count_kernel<<<cgrid, 256, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_SCAN, st, jwins_scan_kernel<<<m, 1024, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_WRITE, st, jwins_write_kernel<<<cgrid, 256, 0, st>>>(a));
-  return DPZ_OK;
+  return dpz::select_nodes<JwPolicy>(m, a, n, ws, static_cast<hipStream_t>(stream));
 }
