@@ -275,6 +275,12 @@ SIGNATURES = {
     "dpz_jwins_chunk_elems": (_i64, []),
     "dpz_jwins_encode_workspace_bytes": (_size, [_int, _i64]),
     "dpz_jwins_encode_nodes": (_int, [_int, _c_void_p, _i64, _c_void_p, _size, _c_void_p]),
+    "dpz_wvgen_tile_width": (_i64, []),
+    "dpz_wavelet_generic_nodes_workspace_bytes": (_size, [_int, _i64, _int, _int]),
+    "dpz_dwt_generic_nodes": (_int, [_int, _c_void_p, _c_void_p, _i64, _int, _c_void_p, _int, _int,
+                                     _c_void_p, _size, _c_void_p]),
+    "dpz_idwt_generic_nodes": (_int, [_int, _c_void_p, _c_void_p, _i64, _int, _c_void_p, _int,
+                                      _c_void_p, _size, _c_void_p]),
     "dpz_fft_nodes_workspace_bytes": (_i64, [_int, _i64]),
     "dpz_rfft_nodes": (_int, [_int, _c_void_p, _c_void_p, _i64, _c_void_p, _size, _c_void_p]),
     "dpz_irfft_nodes": (_int, [_int, _c_void_p, _c_void_p, _i64, _c_void_p, _size, _c_void_p]),

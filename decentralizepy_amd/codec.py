@@ -36,7 +36,9 @@ __all__ = ["DPZ_ACC_NONE", "DPZ_ACC_ACCUMULATE", "DPZ_ACC_ADD", "DPZ_EW_SUB", "D
            "stc_server_fold", "stc_apply_table", "stc_apply_nodes", "topkacc_chunk_elems",
            "topkacc_row_words", "topkacc_node_table", "topkacc_encode_nodes",
            "topkacc_post_nodes", "DwtNodesTable", "IdwtNodesTable", "dwt_sym2_nodes",
-           "idwt_sym2_nodes", "jwins_chunk_elems", "JwinsEncodeTable", "jwins_encode_nodes"]
+           "idwt_sym2_nodes", "jwins_chunk_elems", "JwinsEncodeTable", "jwins_encode_nodes",
+           "wavelet_nodes_tile_width", "wavelet_nodes_workspace", "dwt_generic_nodes",
+           "idwt_generic_nodes"]
 
 
 def _ptr(t):
@@ -1769,6 +1771,58 @@ def idwt_sym2_nodes(table, n, level=4, check_rc=True):
                                         int(level), _stream(table.dev.device))
     if check_rc:
         check(rc, "dpz_idwt_sym2_nodes")
+    return rc
+
+
+def wavelet_nodes_tile_width():
+    """Output pairs (forward) or output positions (inverse) one block of ``dwt_generic_nodes`` /
+    ``idwt_generic_nodes`` owns."""
+    return int(_lib.lib().dpz_wvgen_tile_width())
+
+
+def wavelet_nodes_workspace(m, n, level, wavelet, device):
+    """The workspace of ``dwt_generic_nodes`` / ``idwt_generic_nodes`` for m nodes: the
+    intermediate approximations' ping-pong rows (nothing at level 1)."""
+    nb = int(_lib.lib().dpz_wavelet_generic_nodes_workspace_bytes(int(m), int(n), int(level),
+                                                                  filter_len(wavelet)))
+    return torch.empty(max(4, (nb + 3) // 4), dtype=torch.float32, device=device)
+
+
+def dwt_generic_nodes(table, n, level, wavelet, accumulate=False, workspace=None, check_rc=True):
+    """``wavedec`` (any wavelet of the filter table) of every node of ``table`` (a
+    ``DwtNodesTable``) in ``level`` launches: per node bit for bit ``dpz_dwt_generic(x, x0, n,
+    level, bank, flen, coeffs_x, coeffs_diff, accumulate)`` without a rewind mask.  Every row is
+    16-byte aligned and every node names the same outputs.  Returns the library's code (raises
+    unless it is DPZ_OK when ``check_rc``)."""
+    _require(table.dev, torch.int64, "table")
+    dev = table.dev.device
+    if workspace is None:
+        workspace = wavelet_nodes_workspace(table.m, n, level, wavelet, dev)
+    _require(workspace, torch.float32, "workspace")
+    rc = _lib.lib().dpz_dwt_generic_nodes(
+        table.m, _ptr(table.dev), ctypes.c_void_p(table.host.ctypes.data), int(n), int(level),
+        _ptr(_bank(wavelet, dev)), filter_len(wavelet), 1 if accumulate else 0, _ptr(workspace),
+        workspace.numel() * 4, _stream(dev))
+    if check_rc:
+        check(rc, f"dpz_dwt_generic_nodes({wavelet})")
+    return rc
+
+
+def idwt_generic_nodes(table, n, level, wavelet, workspace=None, check_rc=True):
+    """``waverec`` (any wavelet of the filter table) of every node of ``table`` (an
+    ``IdwtNodesTable``) in ``level`` launches: per node bit for bit ``dpz_idwt_generic(coeffs, n,
+    level, bank, flen, out)``."""
+    _require(table.dev, torch.int64, "table")
+    dev = table.dev.device
+    if workspace is None:
+        workspace = wavelet_nodes_workspace(table.m, n, level, wavelet, dev)
+    _require(workspace, torch.float32, "workspace")
+    rc = _lib.lib().dpz_idwt_generic_nodes(
+        table.m, _ptr(table.dev), ctypes.c_void_p(table.host.ctypes.data), int(n), int(level),
+        _ptr(_bank(wavelet, dev)), filter_len(wavelet), _ptr(workspace), workspace.numel() * 4,
+        _stream(dev))
+    if check_rc:
+        check(rc, f"dpz_idwt_generic_nodes({wavelet})")
     return rc
 
 

@@ -24,42 +24,13 @@
 // writing exactly the next level's length (pywt's one-longer trim) and, at level 1, n outputs.
 // Layout [cA_L, cD_L, ..., cD_1] (pywt.coeffs_to_array), len_l = floor((len_{l-1} + F - 1) / 2).
 // Performance is a non-goal beyond coalescing: the shipped configs run the fused sym2 kernels.
-#include "dpz_common.h"
+#include "dpz_wvgen.h"
 
 namespace dpz {
-
-constexpr int WG_FMAX = 64;
-constexpr int WG_LMAX = 8;
-
-struct WgLevels {
-  int64_t len[WG_LMAX + 1];
-  int64_t doff[WG_LMAX + 1];  // offset of cD_l in the coefficient array
-  int64_t total;
-};
-
-static bool wg_levels(int64_t n, int level, int F, WgLevels* L) {
-  if (n <= 0 || level < 1 || level > WG_LMAX || F < 2 || F > WG_FMAX || (F & 1)) return false;
-  L->len[0] = n;
-  for (int l = 1; l <= level; ++l) {
-    if (L->len[l - 1] < F) return false;
-    L->len[l] = (L->len[l - 1] + F - 1) / 2;
-  }
-  int64_t o = L->len[level];
-  for (int l = level; l >= 1; --l) {
-    L->doff[l] = o;
-    o += L->len[l];
-  }
-  L->total = o;
-  return true;
-}
 
 static size_t wg_ws_floats(const WgLevels& L, int level) {
   // two streams x two ping-pong approximation buffers of the longest intermediate level
   return level >= 2 ? (size_t)4 * (size_t)L.len[1] : 0;
-}
-
-__device__ __forceinline__ int64_t wg_ext(int64_t p, int64_t n) {
-  return p < 0 ? -1 - p : (p >= n ? 2 * n - 1 - p : p);
 }
 
 // the accumulator's value before this pass adds to it: +0 where the encode selected it (the

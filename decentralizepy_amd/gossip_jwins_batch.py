@@ -29,9 +29,11 @@ count:
 * ONE ``dpz_idwt_sym2_nodes`` launch into ``x``, ONE accumulating ``dpz_dwt_sym2_nodes`` launch,
   ONE copy of all rows of ``x`` into ``x0``.
 
-Nothing synchronises with the host inside ``step()``.  sym2 at levels 1-4 only; other wavelets and
-deeper levels stay with ``JwinsRound``.  Ties at the k-th key go to the lowest indices; finite
-models only.
+Nothing synchronises with the host inside ``step()``.  ``JwinsBatchRound`` runs sym2 at levels
+1-4 on the fused kernels; ``JwinsWaveletBatchRound`` runs every other wavelet of the filter table
+and sym2 at levels 5-8 with the same legs on ``dpz_dwt_generic_nodes`` /
+``dpz_idwt_generic_nodes`` (``level`` launches per transform instead of one).  Ties at the k-th
+key go to the lowest indices; finite models only.
 
 ``ops`` (an object with ``tests/jwins_ops.OracleJwinsOps``'s methods) replaces the HIP codec node
 by node on CPU tensors, so the round logic is tested with the gloo backend; the default is the HIP
@@ -79,16 +81,11 @@ class JwinsBatchRound(ShardedRound):
             raise ValueError(
                 f"unknown arguments {sorted(unknown)}: JwinsBatchRound offers neither compressed "
                 "payloads nor another exchange than the all-gather")
-        if wavelet != "sym2" or level not in (1, 2, 3, 4):
-            raise ValueError(f"wavelet {wavelet!r} at level {level}: the batched round runs sym2 "
-                             "at levels 1-4; use gossip_jwins.JwinsRound for the others")
+        self._check_config(wavelet, level)
         super().__init__(adj, x_init, rank, world, group, device)
         self.alpha_list = eval(alpha_list) if isinstance(alpha_list, str) else list(alpha_list)
         self.metadata_cap, self.level, self.wavelet = metadata_cap, level, wavelet
-        M = sym2_coeff_len(self.N, level)
-        if M is None:
-            raise ValueError(f"a model of {self.N} parameters is too short for level {level}")
-        self.M = M
+        self.M = M = self._coeff_len()
         partial = [a for a in self.alpha_list if a < metadata_cap]
         for a in partial:
             if round(a * M) < 1:
@@ -127,10 +124,8 @@ class JwinsBatchRound(ShardedRound):
         if self._hip and m:
             from . import codec
             dev = self.device
-            self._pair = codec.DwtNodesTable(self.x, self.x0, self.wx, self.wc, dev)
+            self._make_transform_tables(codec, dev)
             self._enc = codec.JwinsEncodeTable(self.wc, self.acc, self.wx, self.counter, dev)
-            self._inv = codec.IdwtNodesTable(self.wc, self.x, dev)
-            self._post = codec.DwtNodesTable(self.x, self.x0, None, self.acc, dev)
             self._ws = torch.empty(
                 max(256, int(codec._lib.lib().dpz_jwins_encode_workspace_bytes(m, M))),
                 dtype=torch.uint8, device=dev)
@@ -149,6 +144,32 @@ class JwinsBatchRound(ShardedRound):
                 w_self=(ctypes.c_float * m)(*ws_),
                 local=(ctypes.c_void_p * m)(*self._ptrs(self.wx)),
                 out=(ctypes.c_void_p * m)(*self._ptrs(self.wc)))
+
+    # ---- what depends on the wavelet (JwinsWaveletBatchRound overrides these) -----------------
+    @staticmethod
+    def _check_config(wavelet, level):
+        if wavelet != "sym2" or level not in (1, 2, 3, 4):
+            raise ValueError(f"wavelet {wavelet!r} at level {level}: the batched round runs sym2 "
+                             "at levels 1-4; use JwinsWaveletBatchRound for the others "
+                             "(gossip_jwins.JwinsRound for haar)")
+
+    def _coeff_len(self):
+        M = sym2_coeff_len(self.N, self.level)
+        if M is None:
+            raise ValueError(f"a model of {self.N} parameters is too short for level {self.level}")
+        return M
+
+    def _make_transform_tables(self, codec, dev):
+        self._pair = codec.DwtNodesTable(self.x, self.x0, self.wx, self.wc, dev)
+        self._inv = codec.IdwtNodesTable(self.wc, self.x, dev)
+        self._post = codec.DwtNodesTable(self.x, self.x0, None, self.acc, dev)
+
+    def _transform_pair(self, codec):
+        codec.dwt_sym2_nodes(self._pair, self.N, self.level)
+
+    def _transform_post(self, codec):
+        codec.idwt_sym2_nodes(self._inv, self.N, self.level)
+        codec.dwt_sym2_nodes(self._post, self.N, self.level, accumulate=True)
 
     @staticmethod
     def _ptrs(rows):
@@ -191,7 +212,7 @@ class JwinsBatchRound(ShardedRound):
                 else:  # Wavelet.py:185-192: all of W(x); copied only where it is gathered
                     self._enc.set(j, 0, 0, pv if self.coll else 0)
             self._enc.upload()
-            codec.dwt_sym2_nodes(self._pair, self.N, self.level)
+            self._transform_pair(codec)
             codec.jwins_encode_nodes(self._enc, M, self._ws)
             return
         vals = self.send[self._s_idx:self._s_idx + self._s_val].view(torch.float32)
@@ -261,8 +282,7 @@ class JwinsBatchRound(ShardedRound):
             return
         if self._hip:
             from . import codec
-            codec.idwt_sym2_nodes(self._inv, self.N, self.level)
-            codec.dwt_sym2_nodes(self._post, self.N, self.level, accumulate=True)
+            self._transform_post(codec)
         else:
             for j in range(self.m):
                 self.ops.inverse(self.wc[j], self.N, self.x[j])
@@ -284,3 +304,62 @@ class JwinsBatchRound(ShardedRound):
         self.post()
         mark("post")
         self.round += 1
+
+
+def wavelet_coeff_len(n, level, flen):
+    """Length of pywt's concatenated ``wavedec`` array of n values for a filter of ``flen`` taps
+    (mode "symmetric"), len_l = (len_{l-1} + flen - 1) // 2, or None where a level's input is
+    shorter than the filter (the generic kernels' rule, computed without the library)."""
+    lens, cur = [], int(n)
+    for _ in range(level):
+        if cur < flen:
+            return None
+        cur = (cur + flen - 1) // 2
+        lens.append(cur)
+    return sum(lens) + lens[-1]
+
+
+class JwinsWaveletBatchRound(JwinsBatchRound):
+    """``JwinsBatchRound`` for every (wavelet, level) the generic-filter kernels serve: every name
+    of the filter table (db1-32, sym2-20, coif1-10, bior / rbio, dmey; ``db1`` for the Haar
+    filters) at levels 1-8 except sym2 at levels 1-4.  Same constructor, state rows, ``payload()``,
+    legs and ``step()``; the three transforms are ``level`` launches each, whatever the node
+    count, on ``dpz_dwt_generic_nodes`` / ``dpz_idwt_generic_nodes`` with one workspace allocated
+    here."""
+
+    @staticmethod
+    def _check_config(wavelet, level):
+        from . import codec
+        if wavelet == "haar":
+            raise ValueError("wavelet 'haar' runs the fused haar kernels node after node: use "
+                             "gossip_jwins.JwinsRound (or 'db1', the same filters, here)")
+        codec._check_wavelet(wavelet)
+        if level not in range(1, 9):
+            raise NotImplementedError(f"{wavelet} level-{level} wavedec unsupported: the device "
+                                      "kernels run levels 1-8")
+        if codec._fused(wavelet, level):
+            raise ValueError(f"wavelet {wavelet!r} at level {level} runs the fused kernels: use "
+                             "gossip_jwins_batch.JwinsBatchRound")
+
+    def _coeff_len(self):
+        from . import codec
+        M = wavelet_coeff_len(self.N, self.level, codec.filter_len(self.wavelet))
+        if M is None:
+            # Wavelet's documented case: a level whose input is shorter than the filter
+            raise NotImplementedError(
+                f"{self.wavelet} level-{self.level} wavedec unsupported for n={self.N}")
+        return M
+
+    def _make_transform_tables(self, codec, dev):
+        super()._make_transform_tables(codec, dev)
+        self._wws = codec.wavelet_nodes_workspace(self.m, self.N, self.level, self.wavelet, dev)
+
+    def _transform_pair(self, codec):
+        codec.dwt_generic_nodes(self._pair, self.N, self.level, self.wavelet,
+                                workspace=self._wws)
+
+    def _transform_post(self, codec):
+        codec.idwt_generic_nodes(self._inv, self.N, self.level, self.wavelet,
+                                 workspace=self._wws)
+        codec.dwt_generic_nodes(self._post, self.N, self.level, self.wavelet, accumulate=True,
+                                workspace=self._wws)

@@ -1119,6 +1119,29 @@ size_t dpz_jwins_encode_workspace_bytes(int m, int64_t n);
 int dpz_jwins_encode_nodes(int m, const void* node_table, int64_t n, void* ws, size_t ws_bytes,
                            dpz_stream_t stream);
 
+/* ---- The batched JWINS round's transforms for every wavelet (csrc/dpz_wvgen_nodes.hip) -----------
+ * dpz_dwt_generic_nodes / dpz_idwt_generic_nodes: dpz_dwt_generic / dpz_idwt_generic (no rewind
+ * mask) of m nodes of one length n, one level (1-8) and one filter bank (flen <= 64, even; bank
+ * the DEVICE array of 4 flen floats) in `level` launches whatever m is: the grid is tiles x
+ * (node, stream), a block stages its tile of inputs into LDS once.  The tables, their host copies
+ * and the checks made on them are dpz_dwt_sym2_nodes' / dpz_idwt_sym2_nodes'; per node the result
+ * is bit for bit the single-node call's.  ws: dpz_wavelet_generic_nodes_workspace_bytes(m, n,
+ * level, flen) DEVICE bytes, 16-byte aligned (per node and stream two rows of up4(len_1) floats;
+ * 0 at level 1), any content.  Before anything is enqueued: DPZ_ERR_ARG as for the sym2 forms,
+ * for a null bank and for a misaligned workspace; DPZ_ERR_UNSUPPORTED for m > 32767 and for a
+ * (n, level, flen) that dpz_wavedec_len_generic refuses (a level whose input is shorter than the
+ * filter); DPZ_ERR_WORKSPACE for a null or short workspace at level >= 2.  Timed as "dwt" and
+ * "idwt", one entry per launch.  dpz_wvgen_tile_width: the output pairs (forward) or output
+ * positions (inverse, two outputs each) one block owns.                                         */
+int64_t dpz_wvgen_tile_width(void);
+size_t dpz_wavelet_generic_nodes_workspace_bytes(int m, int64_t n, int level, int flen);
+int dpz_dwt_generic_nodes(int m, const void* table, const void* host_table, int64_t n, int level,
+                          const float* bank, int flen, int accumulate, void* ws, size_t ws_bytes,
+                          dpz_stream_t stream);
+int dpz_idwt_generic_nodes(int m, const void* table, const void* host_table, int64_t n, int level,
+                           const float* bank, int flen, void* ws, size_t ws_bytes,
+                           dpz_stream_t stream);
+
 /* ---- An FFT round of a rank's nodes at once (decentralizepy_amd/gossip_fft.py) -------------------
  * dpz_rfft_nodes: `jobs` forward real FFTs of one even length n >= 4 with a native plan
  * (dpz_fft_native), in one launch set of as many launches as one dpz_rfft of that n: the job is in

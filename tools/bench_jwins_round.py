@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Time a whole-topology JWINS round on one GPU: the batched engine against ``JwinsRound``.
 
-Two shapes, one rank each (no collective is part of the timing), the tutorial's alpha list, sym2
-at level 4, ``metadata_cap = 0.5``:
+Two shapes, one rank each (no collective is part of the timing), the tutorial's alpha list,
+``--wavelet`` at ``--level`` (sym2 at level 4 by default), ``metadata_cap = 0.5``:
 
   ref96     ``96_regular.edges`` x N = 89,834 (the reference's CIFAR LeNet): 96 small models, a
             node's kernels take microseconds, the round is bound by the host;
@@ -16,8 +16,9 @@ and the same seeded "training" step between rounds, so their states stay equal i
 (models, init models, accumulators, counters and payloads; checked after the first two rounds,
 before anything is timed, and after the last round):
 
-  engine     ``gossip_jwins_batch.JwinsBatchRound.step``: one launch set per leg for all nodes,
-             no host synchronisation;
+  engine     ``gossip_jwins_batch.JwinsBatchRound.step`` (sym2 to level 4) or
+             ``JwinsWaveletBatchRound.step`` (every other wavelet and level): one launch set per
+             leg for all nodes, no host synchronisation;
   baseline   ``gossip_jwins.JwinsRound`` through its own legs (``encode_all``, ``exchange``,
              ``fold_all``): each node's kernels as separate calls on three streams, the status
              words read back once per round.  Its ``fold_all`` holds the fold, the inverse, the
@@ -29,9 +30,13 @@ and for the baseline its read-back) and ``wall_ms`` (wall clock until the round'
 completed).  ``--warmup`` untimed rounds, the median over ``--rounds`` rounds, ``--runs`` times
 over; the range over the runs is reported, and a speed-up as the range [baseline min / engine
 max, baseline max / engine min]: a range that contains 1 is no difference.  Prints one JSON line
-per shape.
+per shape.  For a wavelet of the generic-filter kernels the line also holds ``transforms``: the
+three transform launch sets alone (``dwt_generic_nodes`` pair and accumulating pass,
+``idwt_generic_nodes``) against the per-node ``codec.wavedec`` / ``codec.waverec`` calls they
+replace, wall clock from the first call until the device has finished, on scratch rows.
 
     python tools/bench_jwins_round.py [--shapes ref96,c3_16,sw96] [--rounds 50] [--runs 3]
+                                      [--wavelet db4 --level 4]
 """
 import argparse
 import json
@@ -45,8 +50,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from decentralizepy_amd.gossip import read_edges  # noqa: E402
-from decentralizepy_amd.gossip_jwins import JwinsRound  # noqa: E402
-from decentralizepy_amd.gossip_jwins_batch import JwinsBatchRound  # noqa: E402
+from decentralizepy_amd.gossip_jwins import JwinsRound, _al  # noqa: E402
+from decentralizepy_amd import codec  # noqa: E402
+from decentralizepy_amd.gossip_jwins_batch import (JwinsBatchRound,  # noqa: E402
+                                                   JwinsWaveletBatchRound)
 
 ALPHAS = [0.1, 0.15, 0.2, 0.25, 0.3, 0.4, 1.0]  # tutorial/JWINS/config.ini
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -57,8 +64,9 @@ SHAPES = {"ref96": ("96_regular.edges", 89_834), "c3_16": ("regular_16.edges", 2
 class Baseline:
     """``JwinsRound`` with a ``step(mark)`` over its own legs."""
 
-    def __init__(self, adj, x_init, dev):
-        self.eng = JwinsRound(adj, x_init, str(ALPHAS), metadata_cap=0.5, device=dev)
+    def __init__(self, adj, x_init, dev, wavelet, level):
+        self.eng = JwinsRound(adj, x_init, str(ALPHAS), wavelet=wavelet, level=level,
+                              metadata_cap=0.5, device=dev)
         self.x = self.eng.x
 
     def step(self, mark):
@@ -79,8 +87,10 @@ class Baseline:
 
 
 class Engine:
-    def __init__(self, adj, x_init, dev):
-        self.eng = JwinsBatchRound(adj, x_init, ALPHAS, metadata_cap=0.5, device=dev)
+    def __init__(self, adj, x_init, dev, wavelet, level):
+        cls = JwinsBatchRound if codec._fused(wavelet, level) else JwinsWaveletBatchRound
+        self.eng = cls(adj, x_init, ALPHAS, wavelet=wavelet, level=level, metadata_cap=0.5,
+                       device=dev)
         self.x = self.eng.x
 
     def step(self, mark):
@@ -130,6 +140,54 @@ def same_state(eng, base):
     return bool(ok)
 
 
+def time_transforms(e, wavelet, level, reps, runs):
+    """The engine's three transform launch sets against the per-node calls, on scratch rows of
+    the engine's shapes (the engine's state is not touched): wall-clock milliseconds, the median
+    over ``reps``, the range over ``runs`` alternated runs."""
+    m, n, dev = e.m, e.N, e.device
+    wx, wc, acc, out = (torch.zeros(m, _al(t.shape[1]), device=dev)[:, :t.shape[1]]
+                        for t in (e.wx, e.wc, e.acc, e.x))  # rows on 256-byte boundaries
+    pair = codec.DwtNodesTable(e.x, e.x0, wx, wc, dev)
+    inv = codec.IdwtNodesTable(e.wx, out, dev)
+    post = codec.DwtNodesTable(e.x, e.x0, None, acc, dev)
+    ws = codec.wavelet_nodes_workspace(m, n, level, wavelet, dev)
+    kw = dict(wavelet=wavelet)
+
+    def per_node(fn):
+        def run():
+            for j in range(m):
+                fn(j)
+        return run
+
+    sets = {
+        "pair": (lambda: codec.dwt_generic_nodes(pair, n, level, wavelet, workspace=ws),
+                 per_node(lambda j: codec.wavedec(e.x[j], level, x0=e.x0[j], coeffs_x=wx[j],
+                                                  coeffs_diff=wc[j], **kw))),
+        "inverse": (lambda: codec.idwt_generic_nodes(inv, n, level, wavelet, workspace=ws),
+                    per_node(lambda j: codec.waverec(e.wx[j], n, level, out=out[j], **kw))),
+        "post": (lambda: codec.dwt_generic_nodes(post, n, level, wavelet, accumulate=True,
+                                                 workspace=ws),
+                 per_node(lambda j: codec.wavedec(e.x[j], level, x0=e.x0[j], want_x=False,
+                                                  coeffs_diff=acc[j], accumulate=True, **kw))),
+    }
+    res = {}
+    for name, (nodes, single) in sets.items():
+        got = {"nodes_ms": [], "per_node_ms": []}
+        for _ in range(runs):
+            for key, fn in (("nodes_ms", nodes), ("per_node_ms", single)):
+                fn()
+                ts = []
+                for _ in range(reps):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize()
+                    ts.append((time.perf_counter() - t0) * 1e3)
+                got[key].append(round(float(np.median(ts)), 4))
+        res[name] = got
+    return res
+
+
 def run_shape(args, name, dev):
     edges, n = SHAPES[name]
     adj = read_edges(os.path.join(GOLDEN, edges))
@@ -142,7 +200,8 @@ def run_shape(args, name, dev):
     gen = torch.Generator(device=dev).manual_seed(1)
     x0 = torch.randn(m, n, device=dev, generator=gen)
     noise = torch.randn(n, device=dev, generator=gen)  # the "training" step, rolled per node
-    variants = {"engine": Engine(adj, x0, dev), "baseline": Baseline(adj, x0, dev)}
+    variants = {"engine": Engine(adj, x0, dev, args.wavelet, args.level),
+                "baseline": Baseline(adj, x0, dev, args.wavelet, args.level)}
     del x0
     eng, base = variants["engine"], variants["baseline"]
 
@@ -182,7 +241,7 @@ def run_shape(args, name, dev):
     torch.cuda.synchronize()
     same = same_state(eng, base)
     res = {"shape": name, "device": torch.cuda.get_device_name(0), "nodes": m, "n": n,
-           "m_len": eng.eng.M, "alpha_list": ALPHAS, "rounds": args.rounds, "runs": args.runs,
+           "m_len": eng.eng.M, "wavelet": args.wavelet, "level": args.level, "alpha_list": ALPHAS, "rounds": args.rounds, "runs": args.runs,
            "warmup": args.warmup + 2, "total_rounds": r, "equal_after_two_rounds": True,
            "results_equal": same}
     for v in variants:
@@ -194,6 +253,9 @@ def run_shape(args, name, dev):
     for leg in ("encode", "fold_post", "device_ms", "host_ms", "wall_ms"):
         res[f"{leg}_speedup"] = [round(b[leg]["min_ms"] / e[leg]["max_ms"], 2),
                                  round(b[leg]["max_ms"] / e[leg]["min_ms"], 2)]
+    if not codec._fused(args.wavelet, args.level):
+        res["transforms"] = time_transforms(eng.eng, args.wavelet, args.level, args.rounds,
+                                            args.runs)
     print(json.dumps(res), flush=True)
     if not same:
         raise SystemExit(f"{name}: the engine's and the baseline's states differ")
@@ -205,6 +267,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=50)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--wavelet", default="sym2")
+    ap.add_argument("--level", type=int, default=4)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_jwins_round needs a ROCm GPU; there is no CPU path")
