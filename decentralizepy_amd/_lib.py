@@ -294,6 +294,10 @@ SIGNATURES = {
     "dpz_cplx_encode_workspace_bytes": (_size, [_int, _i64]),
     "dpz_cplx_encode_nodes": (_int, [_int, _c_void_p, _i64, _i64, _int, _c_void_p, _size,
                                      _c_void_p]),
+    "dpz_elias_bound_bytes": (_i64, [_i64, _i64]),
+    "dpz_wire_nodes_workspace_bytes": (_size, [_int, _i64]),
+    "dpz_wire_encode_nodes": (_int, [_int, _c_void_p, _c_void_p, _int, _c_void_p, _c_void_p,
+                                     _c_void_p, _size, _c_void_p]),
 }
 
 _lib = None

@@ -38,7 +38,8 @@ __all__ = ["DPZ_ACC_NONE", "DPZ_ACC_ACCUMULATE", "DPZ_ACC_ADD", "DPZ_EW_SUB", "D
            "topkacc_post_nodes", "DwtNodesTable", "IdwtNodesTable", "dwt_sym2_nodes",
            "idwt_sym2_nodes", "jwins_chunk_elems", "JwinsEncodeTable", "jwins_encode_nodes",
            "wavelet_nodes_tile_width", "wavelet_nodes_workspace", "dwt_generic_nodes",
-           "idwt_generic_nodes"]
+           "idwt_generic_nodes", "elias_bound_bytes", "WireNodesTable", "wire_nodes_workspace",
+           "wire_encode_nodes"]
 
 
 def _ptr(t):
@@ -1882,6 +1883,64 @@ def jwins_encode_nodes(table, n, workspace=None):
         raise ValueError("a node table with a null row: c, acc and vals_src of every node, "
                          "idx_out and val_out of every node with k >= 1")
     return _encode_nodes("jwins", table.dev, m, n, (), workspace)
+
+
+def elias_bound_bytes(k, n):
+    """A slot size for the Elias stream of k ascending indices below n (``dpz_elias_bound_bytes``):
+    never below a real stream rounded up to whole words plus 16, far below ``dpz_elias_max_bytes``
+    for spread-out indices."""
+    return int(_lib.lib().dpz_elias_bound_bytes(int(k), int(n)))
+
+
+class WireNodesTable(JwinsEncodeTable):
+    """The node table of ``wire_encode_nodes``: 8 words per node {idx or 0, val, count, idx_out or
+    0, val_out or 0, idx_cap bytes, val_cap bytes, 0}.  ``set(j, idx, val, count, ...)`` fills
+    node j's words on the host (tensors or addresses; None / 0: a full share for ``idx``, size only
+    for an output); ``upload()`` enqueues the copy to the DEVICE words without waiting for it."""
+
+    def __init__(self, m, device):
+        self.m = m
+        self.host = np.zeros((max(1, m), 8), dtype=np.uint64)
+        self.dev = torch.zeros(max(1, m), 8, dtype=torch.int64, device=device)
+
+    def set(self, j, idx, val, count, idx_out=None, val_out=None, idx_cap=0, val_cap=0):
+        self.host[j] = (self._addr(idx), self._addr(val), int(count), self._addr(idx_out),
+                        self._addr(val_out), int(idx_cap), int(val_cap), 0)
+
+
+def wire_nodes_workspace(m, max_count, device, workspace=None):
+    """A uint8 device tensor of ``dpz_wire_nodes_workspace_bytes(m, max_count)`` bytes
+    (``workspace`` itself when it is large enough)."""
+    need = max(256, int(_lib.lib().dpz_wire_nodes_workspace_bytes(int(m), int(max_count))))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+    return workspace
+
+
+def wire_encode_nodes(table, sizes, status, precision=0, workspace=None, check_rc=True):
+    """The wire streams of every node of ``table`` (an uploaded ``WireNodesTable``) in three
+    launches, nothing read back: per node the Elias-gamma stream of its indices, byte for byte
+    ``elias_encode``'s (none for a full share), and the block-floating stream of its values, byte
+    for byte ``fpz_encode(val, precision)``'s, each into its slot where it has one and fits it.
+    ``sizes`` (device int64, (m, 2)) gets every node's index and value stream bytes, written or
+    not; ``status`` (device int32, m) gets 0 or the OR of 1 (indices not strictly increasing), 2
+    (index slot too short), 4 (value slot too short).  ``workspace``: ``wire_nodes_workspace``'s
+    tensor (allocated here when None).  Returns the library's code (raises unless it is DPZ_OK
+    when ``check_rc``)."""
+    _require(table.dev, torch.int64, "table")
+    _require(sizes, torch.int64, "sizes")
+    _require(status, torch.int32, "status")
+    m, dev = table.m, table.dev.device
+    if sizes.numel() < 2 * m or status.numel() < m:
+        raise ValueError(f"sizes and status hold {sizes.numel()} and {status.numel()} words, "
+                         f"{m} nodes need {2 * m} and {m}")
+    workspace = wire_nodes_workspace(m, int(table.host[:m, 2].max()) if m else 0, dev, workspace)
+    rc = _lib.lib().dpz_wire_encode_nodes(
+        m, _ptr(table.dev), ctypes.c_void_p(table.host.ctypes.data), int(precision), _ptr(sizes),
+        _ptr(status), _ptr(workspace), workspace.numel(), _stream(dev))
+    if check_rc:
+        check(rc, "dpz_wire_encode_nodes")
+    return rc
 
 
 class FftNodesTable(_WordTable):

@@ -19,10 +19,10 @@
 // counts and gap sums) -> write (one wave per chunk re-parses its true path from LDS and writes
 // first + running gap sums).
 #include "dpz_common.h"
+#include "dpz_wire.h"
 
 namespace dpz {
 
-constexpr int EL_CODES = 1024;   // codes per encode block (4 per thread)
 constexpr int EL_CHUNK = 1024;   // bits per decode chunk
 constexpr int EL_CW = EL_CHUNK / 32;
 constexpr int EL_STAGE = EL_CW + 4;  // staged words per chunk (a code may run 62 bits past)
@@ -37,8 +37,6 @@ struct ElHdr {
   uint32_t pad;
   uint64_t count;   // decode: number of values (codes + 1)
 };
-
-__device__ __forceinline__ uint32_t code_len(uint32_t g) { return 2u * (31u - __clz(g)) + 1u; }
 
 // ---------------------------------------------------------------- encode
 __global__ void __launch_bounds__(256) elias_count_kernel(const int32_t* __restrict__ idx,

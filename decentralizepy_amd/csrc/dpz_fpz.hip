@@ -25,69 +25,14 @@
 // as whole words).  Decode: 1 launch, one wave per block, sync-free (n comes from the host copy
 // of the header).
 #include "dpz_common.h"
+#include "dpz_wire.h"
 
 namespace dpz {
-
-constexpr int FZ_B = 256;                      // values per block (4 per lane of one wave)
-constexpr int FZ_MAXW = 1 + 8 + 8 * 8 + 8 * 23;  // words of a full block at w = 8, mb = 23
-constexpr uint32_t FZ_MAGIC = 0x5A465044u;     // "DPFZ"
-constexpr int64_t FZ_MAXN = int64_t(1) << 30;  // values a stream (block offsets stay 32-bit)
 
 struct FzHdr {
   uint64_t words;   // block-area words
   uint64_t nbytes;  // whole stream
 };
-
-__device__ __forceinline__ int fz_bits(uint32_t v) { return v ? 32 - __clz(v) : 0; }
-
-__device__ __forceinline__ uint32_t fz_words(int cnt, int w, int mb) {
-  return 1u + (uint32_t)((cnt + 31) / 32) + (uint32_t)((cnt * w + 31) / 32) +
-         (uint32_t)((cnt * mb + 31) / 32);
-}
-
-// the 4 values of this lane (block-relative j = 4 * lane + e); exponent range over the wave
-__device__ __forceinline__ void fz_load(const float* __restrict__ x, int64_t n, int64_t b,
-                                        int prec, int lane, uint32_t u[4], int* cnt_out,
-                                        uint32_t* emin_out, int* w_out) {
-  const int64_t base = b * FZ_B;
-  const int cnt = (int)((n - base) < FZ_B ? (n - base) : FZ_B);
-  const int64_t i0 = base + 4 * lane;
-  if (4 * lane + 3 < cnt && aligned16(x)) {
-    const float4 v = *reinterpret_cast<const float4*>(x + i0);
-    u[0] = __float_as_uint(v.x); u[1] = __float_as_uint(v.y);
-    u[2] = __float_as_uint(v.z); u[3] = __float_as_uint(v.w);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) u[e] = (4 * lane + e < cnt) ? __float_as_uint(x[i0 + e]) : 0u;
-  }
-  if (prec < 32) {  // keep the top `prec` bits; from 10 bits on a NaN keeps a mantissa bit
-    const uint32_t keep = ~((1u << (32 - prec)) - 1u);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const uint32_t t = u[e] & keep;
-      const bool nan = (u[e] & 0x7F800000u) == 0x7F800000u && (u[e] & 0x7FFFFFu) != 0u;
-      u[e] = (prec >= 10 && nan && (t & 0x7FFFFFu) == 0u) ? (t | 0x400000u) : t;
-    }
-  }
-  uint32_t lo = 255u, hi = 0u;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    if (4 * lane + e < cnt) {
-      const uint32_t ex = (u[e] >> 23) & 0xFFu;
-      lo = ex < lo ? ex : lo;
-      hi = ex > hi ? ex : hi;
-    }
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const uint32_t l2 = __shfl_xor(lo, d, 64), h2 = __shfl_xor(hi, d, 64);
-    lo = l2 < lo ? l2 : lo;
-    hi = h2 > hi ? h2 : hi;
-  }
-  *cnt_out = cnt;
-  *emin_out = lo;
-  *w_out = fz_bits(hi - lo);
-}
 
 __global__ void __launch_bounds__(256) fz_size_kernel(const float* __restrict__ x, int64_t n,
                                                       int64_t nblk, int prec, int mb,
@@ -127,15 +72,6 @@ __global__ void __launch_bounds__(1024) fz_scan_kernel(int64_t n, int64_t nblk, 
   }
 }
 
-// OR `v` (at most 32 bits wide, `bits` of them) into the LDS bit stream at bit `pos`
-__device__ __forceinline__ void fz_put(uint32_t* s, uint32_t pos, uint32_t v, int bits) {
-  if (!bits) return;
-  const uint32_t wi = pos >> 5, sh = pos & 31u;
-  const uint64_t v64 = (uint64_t)v << sh;
-  if ((uint32_t)v64) atomicOr(&s[wi], (uint32_t)v64);
-  if (sh + bits > 32 && (uint32_t)(v64 >> 32)) atomicOr(&s[wi + 1], (uint32_t)(v64 >> 32));
-}
-
 __global__ void __launch_bounds__(256) fz_pack_kernel(const float* __restrict__ x, int64_t n,
                                                       int64_t nblk, int prec, int mb,
                                                       uint32_t* __restrict__ out32) {
@@ -143,31 +79,8 @@ __global__ void __launch_bounds__(256) fz_pack_kernel(const float* __restrict__ 
   const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t b = (int64_t)blockIdx.x * 4 + wid;
   if (b >= nblk) return;  // whole waves only: no block-wide barrier below
-  uint32_t* s = stage[wid];
-  for (int q = lane; q < FZ_MAXW + 1; q += 64) s[q] = 0u;
-  uint32_t u[4], emin;
-  int cnt, w;
-  fz_load(x, n, b, prec, lane, u, &cnt, &emin, &w);
-  const uint32_t ps = 1u, pe = ps + (uint32_t)((cnt + 31) / 32);
-  const uint32_t pm = pe + (uint32_t)((cnt * w + 31) / 32);
-  const uint32_t nw = pm + (uint32_t)((cnt * mb + 31) / 32);
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const uint32_t j = 4u * lane + e;
-    if ((int)j < cnt) {
-      fz_put(s + ps, j, u[e] >> 31, 1);
-      fz_put(s + pe, j * w, ((u[e] >> 23) & 0xFFu) - emin, w);
-      fz_put(s + pm, j * mb, (u[e] & 0x7FFFFFu) >> (23 - mb), mb);
-    }
-  }
-  if (lane == 0) s[0] = emin | ((uint32_t)w << 8) | ((uint32_t)mb << 16);
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
   const uint32_t* table = out32 + 4;
-  uint32_t* dst = out32 + 4 + nblk + 1 + table[b];
-  for (uint32_t q = lane; q < nw; q += 64) dst[q] = s[q];
+  fz_pack_block(x, n, b, prec, mb, lane, stage[wid], out32 + 4 + nblk + 1 + table[b]);
 }
 
 __device__ __forceinline__ uint32_t fz_get(const uint32_t* __restrict__ p, uint32_t pos, int bits) {
@@ -232,17 +145,6 @@ __global__ void __launch_bounds__(256) fz_decode_kernel(const uint32_t* __restri
 }
 
 static inline size_t fz_al256(size_t v) { return (v + 255) & ~size_t(255); }
-
-// stored precision (32 = lossless) and mantissa bits of a requested precision; -1 if invalid
-static inline int fz_mbits(int precision, int* prec_out) {
-  if (precision < 0) return -1;
-  if (precision == 0 || precision >= 32) {
-    *prec_out = 32;
-    return 23;
-  }
-  *prec_out = precision;
-  return precision > 9 ? precision - 9 : 0;
-}
 
 }  // namespace dpz
 

@@ -35,6 +35,10 @@ and sym2 at levels 5-8 with the same legs on ``dpz_dwt_generic_nodes`` /
 ``dpz_idwt_generic_nodes`` (``level`` launches per transform instead of one).  Ties at the k-th
 key go to the lowest indices; finite models only.
 
+``wire_bytes()`` / ``wire_payload(q)`` (``gossip_round.WireCoded``) give what the round's payloads
+are on the wire with ``compression_class = EliasFpzip`` at ``float_precision``; ``step()`` does not
+call them.
+
 ``ops`` (an object with ``tests/jwins_ops.OracleJwinsOps``'s methods) replaces the HIP codec node
 by node on CPU tensors, so the round logic is tested with the gloo backend; the default is the HIP
 codec (no CPU fallback).
@@ -46,7 +50,7 @@ import torch
 
 from .gossip import mh_weights
 from .gossip_jwins import ALIGN, JwinsRound, _al
-from .gossip_round import ShardedRound
+from .gossip_round import ShardedRound, WireCoded
 
 LEGS = ("encode", "exchange", "fold", "post")
 
@@ -65,7 +69,7 @@ def sym2_coeff_len(n, level):
     return sum(lens) + lens[-1]
 
 
-class JwinsBatchRound(ShardedRound):
+class JwinsBatchRound(WireCoded, ShardedRound):
     """Nodes [lo, hi) of a topology on this rank; ``step()`` runs one JWINS round of every node.
 
     Node i is uid i.  Per-node state, rows of (hi - lo, ·) tensors whose rows start on 256-byte
@@ -76,7 +80,7 @@ class JwinsBatchRound(ShardedRound):
 
     def __init__(self, adj, x_init, alpha_list="[0.1, 0.2, 0.3, 0.4, 1.0]", rank=0, world=1,
                  group=None, wavelet="sym2", level=4, metadata_cap=0.5, device=None, ops=None,
-                 **unknown):
+                 float_precision=0, **unknown):
         if unknown:
             raise ValueError(
                 f"unknown arguments {sorted(unknown)}: JwinsBatchRound offers neither compressed "
@@ -93,6 +97,7 @@ class JwinsBatchRound(ShardedRound):
                                  "coefficients: an empty payload is not a share")
         self._hip = ops is None
         self.ops = ops
+        self._init_wire(float_precision, [round(a * M) for a in partial])
         # JWINS.__init__: random.seed(uid) in every node process; every rank replays every node's
         # draws, so every payload's size and place are known everywhere
         self.rngs = [random.Random(uid) for uid in range(self.n_nodes)]
@@ -195,10 +200,27 @@ class JwinsBatchRound(ShardedRound):
             return None, self.wx[q - self.lo]  # the full W(x), no copy on one rank
         return None, buf[pv:pv + self.M].view(torch.float32)
 
+    # ---- the wire layer's hooks (gossip_round.WireCoded) --------------------------------------
+    def _wire_views(self):
+        vals = self.send[self._s_idx:self._s_idx + self._s_val].view(torch.float32)
+        views = []
+        for j in range(self.m):
+            partial, k, oi, ov = self._lay[self.lo + j]
+            views.append((self.send[oi:oi + k], vals[ov:ov + k]) if partial
+                         else (None, self.wx[j]))
+        return self.M, views
+
+    def _wire_message(self, q, indices, params):
+        if indices is None:  # Wavelet.py:185-192: a full share carries its coefficients only
+            return {"params": params}
+        return {"alpha": self.alphas[q], "params": params, "indices": indices,
+                "send_partial": True}  # key order of reference Wavelet.py:223-229
+
     # ---- the legs of a round -----------------------------------------------------------------
     def encode(self):
         """W(x), W(x - x0) and the payload of every owned node; acc and the counter updated."""
         m, M = self.m, self.M
+        self._wire_reset()
         if not m:
             return
         if self._hip:

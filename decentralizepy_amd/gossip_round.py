@@ -1,8 +1,9 @@
 """What the whole-topology round engines (gossip.py, gossip_jwins.py, gossip_jwins_batch.py,
 gossip_subsampling.py, gossip_epidemic.py, gossip_choco.py, gossip_quant.py, gossip_stc.py,
 gossip_topkacc.py, gossip_fft.py) share:
-``ShardedRound``, the sharding of the nodes over the ranks, and ``PackedRowRound``, the packed row
-per node that one all-gather exchanges."""
+``ShardedRound``, the sharding of the nodes over the ranks, ``PackedRowRound``, the packed row
+per node that one all-gather exchanges, and ``WireCoded``, the EliasFpzip wire streams of a round's
+payloads in one batched call."""
 import math
 
 import numpy as np
@@ -53,6 +54,112 @@ class ShardedRound:
     def all_gather(self, recv, send):
         import torch.distributed as dist  # looked up per call: the tests patch the module
         dist.all_gather_into_tensor(recv, send, group=self.group)
+
+
+class WireCoded:
+    """The wire layer of an engine whose payloads are ``(idx or None, vals)`` lists with counts the
+    host knows: what the per-node plugins would send with ``compression_class = EliasFpzip`` (the
+    reference's ``compression/EliasFpzip.py``), coded for all owned nodes by ONE
+    ``codec.wire_encode_nodes`` call.  The engine calls ``_init_wire`` from its constructor and
+    ``_wire_reset`` from ``encode()``, sets ``_hip`` and provides two hooks:
+
+    * ``_wire_views()``: ``(n, [(idx or None, vals), ...])``, device views of the owned nodes'
+      payloads of the last encode in node order, indices below n;
+    * ``_wire_message(q, indices, params)``: the dict the plugin puts on the wire for node q
+      (``indices`` None for a full share)."""
+
+    def _init_wire(self, float_precision, partial_ks):
+        self.float_precision = int(float_precision)
+        if self.float_precision < 0:
+            raise ValueError("float_precision must be >= 0 (0 or >= 32: lossless)")
+        # a one-index share is a valid round (the engines have always run it) but has no Elias
+        # stream: the configuration is refused where the wire layer is asked for
+        self._wire_low = min((k for k in partial_ks if k < 2), default=None)
+        self._wire_tab = self._wire_ws = self._wire_sizes = self._wire_streams = None
+        self._wire_encoded = False
+
+    def _wire_reset(self):
+        """A new encode: what was coded for the last one is void."""
+        self._wire_encoded = True
+        self._wire_sizes = self._wire_streams = None
+
+    def _wire_call(self, slots):
+        """One batched call over the owned nodes; with ``slots`` into per-node slots of one new
+        buffer.  Returns (sizes, status, buffer or None, [(idx offset or None, val offset)])."""
+        if self._wire_low is not None:
+            raise ValueError(f"a partial share of k = {self._wire_low} indices: the Elias index "
+                             "stream needs two (the reference's Elias.compress raises IndexError)")
+        if not self._hip:
+            raise NotImplementedError("the wire streams are coded by the HIP codec only; the CPU "
+                                      "stand-in has no coder")
+        if not self._wire_encoded:
+            raise RuntimeError("no round has been encoded yet")
+        from . import codec
+        n, views = self._wire_views()
+        m = len(views)
+        if self._wire_tab is None:
+            self._wire_tab = codec.WireNodesTable(m, self.device)
+        lib = codec._lib.lib()
+        caps, total = [], 0
+        for idx, vals in views if slots else ():
+            ci = codec.elias_bound_bytes(vals.numel(), n) if idx is not None else 0
+            cv = int(lib.dpz_fpz_max_bytes(vals.numel()))
+            caps.append((total, ci, total + ci, cv))
+            total += ci + cv
+        buf = torch.empty(max(4, total), dtype=torch.uint8, device=self.device) if slots else None
+        for j, (idx, vals) in enumerate(views):
+            if slots:
+                oi, ci, ov, cv = caps[j]
+                base = buf.data_ptr()
+                self._wire_tab.set(j, idx, vals, vals.numel(), base + oi if ci else 0, base + ov,
+                                   ci, cv)
+            else:
+                self._wire_tab.set(j, idx, vals, vals.numel())
+        self._wire_tab.upload()
+        sizes = torch.empty(max(1, m), 2, dtype=torch.int64, device=self.device)
+        status = torch.empty(max(1, m), dtype=torch.int32, device=self.device)
+        if m:
+            self._wire_ws = codec.wire_nodes_workspace(
+                m, max(v.numel() for _, v in views), self.device, self._wire_ws)
+            codec.wire_encode_nodes(self._wire_tab, sizes, status, self.float_precision,
+                                    self._wire_ws)
+        self._wire_sizes = sizes[:m]
+        return sizes[:m], status[:m], buf, [(oi if ci else None, ov) for oi, ci, ov, _ in caps]
+
+    def wire_bytes(self):
+        """Device int64 ``(m, 2)``: the bytes of the index stream (0 for a full share) and of the
+        value stream of every owned node's payload of the last ``encode()`` / ``step()``, as
+        ``EliasFpzip`` codes them at this engine's ``float_precision``.  One batched size-only
+        call of two launches; nothing synchronises with the host.  The pickle framing that the
+        reference's ``TCP.encrypt`` adds is not counted: it is made on the host and is the same
+        for every message of a configuration."""
+        if self._wire_sizes is None:
+            self._wire_call(False)
+        return self._wire_sizes
+
+    def wire_payload(self, q):
+        """The dict the per-node plugin would put on the wire for owned node q after the last
+        ``encode()`` / ``step()``: ``params`` (and ``indices`` of a partial share) as uint8 numpy
+        streams that ``compression.EliasFpzip`` decodes, ``alpha`` and ``send_partial`` as the
+        plugin sets them.  The first call after an encode codes every owned node in one batched
+        call, into slots of ``dpz_elias_bound_bytes`` / ``dpz_fpz_max_bytes`` bytes, and brings
+        the streams to the host (one synchronisation); later calls read that cache."""
+        if not self.lo <= q < self.hi:
+            raise ValueError(f"node {q} is not one of this rank's nodes [{self.lo}, {self.hi})")
+        if self._wire_streams is None:
+            sizes, status, buf, offs = self._wire_call(True)
+            host = torch.empty(buf.numel(), dtype=torch.uint8, pin_memory=True)
+            host.copy_(buf, non_blocking=True)
+            sizes, status = sizes.cpu().numpy(), status.cpu().numpy()  # waits for all three
+            if status.any():
+                raise RuntimeError(f"wire streams of nodes {np.flatnonzero(status).tolist()} "
+                                   f"refused (status {status[status != 0].tolist()})")
+            host = host.numpy()
+            self._wire_streams = [
+                (None if oi is None else host[oi:oi + nb_i].copy(), host[ov:ov + nb_v].copy())
+                for (oi, ov), (nb_i, nb_v) in zip(offs, sizes.tolist())]
+        indices, params = self._wire_streams[q - self.lo]
+        return self._wire_message(q, indices, params)
 
 
 class PackedRowRound(ShardedRound):

@@ -34,19 +34,19 @@ import ctypes
 import torch
 
 from .gossip import mh_weights
-from .gossip_round import PackedRowRound, up4
+from .gossip_round import PackedRowRound, WireCoded, up4
 
 HEADER = PackedRowRound.HEADER
 
 
-class TopKAccRound(PackedRowRound):
+class TopKAccRound(WireCoded, PackedRowRound):
     """Nodes [lo, hi) of a topology on this rank; ``step()`` runs one round.  ``x`` is a stable
     tensor of the owned nodes' models: the caller applies its local training to it in place
     between rounds."""
 
     def __init__(self, adj, x_init, alpha, accumulate_averaging_changes=False, metadata_cap=1.0,
                  rank=0, world=1, group=None, device=None, encode=None, fold=None, post=None,
-                 **unknown):
+                 float_precision=0, **unknown):
         """adj: adjacency sets of all nodes; x_init: (hi - lo, N) fp32, this rank's nodes' models.
         ``encode(x, x0, acc, counter, k, avg) -> (idx, vals)`` (one node, in place on acc and
         counter), ``fold(local, payloads, weights, w_self, out)`` (``GossipRound``'s) and
@@ -71,6 +71,7 @@ class TopKAccRound(PackedRowRound):
                              "use gossip_subsampling.SubSamplingRound for tiny random shares")
         self._hip = not any(injected)
         self._encode, self._fold, self._post = encode, fold, post
+        self._init_wire(float_precision, [self.k])
         self.cap = up4(self.k)
         stride = up4(N)  # every row 16-byte aligned
         self._state = torch.zeros(4, max(1, m), stride, dtype=torch.float32, device=self.device)
@@ -97,6 +98,14 @@ class TopKAccRound(PackedRowRound):
         """``(idx, vals)`` of node q's payload of its last encode (an owned node; any node after
         an all-gather)."""
         return self._pay(self._row(q))
+
+    # ---- the wire layer's hooks (gossip_round.WireCoded) -----------------------------------------
+    def _wire_views(self):
+        return self.N, [self._pay(self.send[j]) for j in range(self.m)]
+
+    def _wire_message(self, q, indices, params):
+        return {"alpha": self.alpha, "indices": indices, "params": params,
+                "send_partial": True}  # key order of reference PartialModel.py:235-246
 
     def _write_row(self, row, idx, vals):
         idx = torch.as_tensor(idx, dtype=torch.int32)
@@ -154,6 +163,7 @@ class TopKAccRound(PackedRowRound):
     # ---- the legs of a round --------------------------------------------------------------------
     def encode(self):
         """Every owned node's selection into its row; acc and the counter updated."""
+        self._wire_reset()
         if self._hip:
             from . import codec
             if self.m:

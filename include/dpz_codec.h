@@ -1213,6 +1213,48 @@ size_t dpz_cplx_encode_workspace_bytes(int m, int64_t n);
 int dpz_cplx_encode_nodes(int m, const void* node_table, int64_t n, int64_t k, int acc_mode,
                           void* ws, size_t ws_bytes, dpz_stream_t stream);
 
+/* ---- The wire streams of a rank's nodes at once (csrc/dpz_wire_nodes.hip) ------------------------
+ * dpz_wire_encode_nodes: the index stream and the value stream of m nodes, every node with its own
+ * count, in THREE launches whatever m is (size, a 1-block-per-node scan, pack) and with no host
+ * synchronisation.  table is a DEVICE array of m entries of 8 64-bit words {idx or 0, val, count,
+ * idx_out or 0, val_out or 0, idx_cap bytes, val_cap bytes, 0}; host_table is its HOST copy, on
+ * which every check is made before anything is enqueued.  Per node:
+ *   idx != 0   a partial share: idx[0, count) ascending int32, count >= 2.  The index stream is
+ *              byte for byte dpz_elias_encode's (the reference's Elias.compress).
+ *   idx == 0   a full share: no index stream, 0 index bytes.
+ *   the value stream is byte for byte dpz_fpz_encode(val, count, precision); count may be 0.
+ *   sizes[2 j], sizes[2 j + 1] (DEVICE int64) = the index and value stream bytes of node j,
+ *   whether or not they are written.
+ *   An output pointer of 0 means size only.  A stream is written when it fits its slot, counted
+ *   in whole 32-bit words: round_up(bytes, 4) <= cap.  Nothing past the stream's last byte is
+ *   changed.  A stream that does not fit is not written at all.
+ *   status[j] (DEVICE uint32, written for every node): 0, or the OR of 1 (a zero or negative gap:
+ *   the index stream is not written and its reported length means nothing; the value stream is
+ *   unaffected), 2 (the index slot is too short), 4 (the value slot is too short).  Another
+ *   node's streams never depend on it.
+ * With no output pointer in the whole table the pack launch is not enqueued (two launches).  No
+ * float atomics; the result does not depend on the grid.  The launches are timed as "fpz_size",
+ * "fpz_scan" and "fpz_pack".  ws: dpz_wire_nodes_workspace_bytes(m, largest count) DEVICE bytes
+ * (0 for m < 1 or a count outside [0, 2^30]), 8-byte aligned, any content.
+ * Before anything is enqueued: DPZ_ERR_ARG for m < 1, a null or misaligned table, sizes, status
+ * or workspace pointer (8, 8, 4, 8 bytes), a null host table, a count outside [0, 2^30], a null
+ * val with count > 0, idx with count < 2 (the reference raises IndexError), idx_out without idx,
+ * a list or slot pointer that is not 4-byte aligned, a negative cap, a nonzero eighth word;
+ * DPZ_ERR_UNSUPPORTED for a negative precision and m > 65535; DPZ_ERR_WORKSPACE for a null or
+ * short workspace.
+ * dpz_elias_bound_bytes (host only): a slot size for the Elias stream of k ascending indices
+ * below n.  The gaps sum to at most n - 1, a code takes 2 floor(log2 g) + 1 bits and log2 is
+ * concave, so the code bits are at most (k-1) (2 log2((n-1)/(k-1)) + 1); the result is that bound
+ * in dpz_elias_max_bytes' convention (+128 bits, whole 32-bit words, +16 bytes).  Never below
+ * round_up(bytes, 4) + 16 of a real stream, equal to it when every gap is the same power of two
+ * and n - 1 their sum, never above dpz_elias_max_bytes(k) (which allows 63 bits a code); 0 for
+ * k < 2, dpz_elias_max_bytes(k) for n < k.                                                       */
+int64_t dpz_elias_bound_bytes(int64_t k, int64_t n);
+size_t dpz_wire_nodes_workspace_bytes(int m, int64_t max_count);
+int dpz_wire_encode_nodes(int m, const void* table, const void* host_table, int precision,
+                          int64_t* sizes, uint32_t* status, void* ws, size_t ws_bytes,
+                          dpz_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
