@@ -298,6 +298,10 @@ SIGNATURES = {
     "dpz_wire_nodes_workspace_bytes": (_size, [_int, _i64]),
     "dpz_wire_encode_nodes": (_int, [_int, _c_void_p, _c_void_p, _int, _c_void_p, _c_void_p,
                                      _c_void_p, _size, _c_void_p]),
+    "dpz_fpz_bound_bytes": (_i64, [_i64, _int]),
+    "dpz_wire_decode_nodes_workspace_bytes": (_size, [_int, _i64, _i64]),
+    "dpz_wire_decode_nodes": (_int, [_int, _c_void_p, _c_void_p, _int, _c_void_p, _c_void_p,
+                                     _size, _c_void_p]),
 }
 
 _lib = None

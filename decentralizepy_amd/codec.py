@@ -39,7 +39,8 @@ __all__ = ["DPZ_ACC_NONE", "DPZ_ACC_ACCUMULATE", "DPZ_ACC_ADD", "DPZ_EW_SUB", "D
            "idwt_sym2_nodes", "jwins_chunk_elems", "JwinsEncodeTable", "jwins_encode_nodes",
            "wavelet_nodes_tile_width", "wavelet_nodes_workspace", "dwt_generic_nodes",
            "idwt_generic_nodes", "elias_bound_bytes", "WireNodesTable", "wire_nodes_workspace",
-           "wire_encode_nodes"]
+           "wire_encode_nodes", "fpz_bound_bytes", "WireDecodeTable", "wire_decode_workspace",
+           "wire_decode_nodes"]
 
 
 def _ptr(t):
@@ -1940,6 +1941,59 @@ def wire_encode_nodes(table, sizes, status, precision=0, workspace=None, check_r
         _ptr(status), _ptr(workspace), workspace.numel(), _stream(dev))
     if check_rc:
         check(rc, "dpz_wire_encode_nodes")
+    return rc
+
+
+def fpz_bound_bytes(n, precision=0):
+    """The largest block-floating stream of n values at a precision (``dpz_fpz_bound_bytes``):
+    ``dpz_fpz_max_bytes(n)`` when lossless, smaller with fewer mantissa bits."""
+    return int(_lib.lib().dpz_fpz_bound_bytes(int(n), int(precision)))
+
+
+class WireDecodeTable(WireNodesTable):
+    """The node table of ``wire_decode_nodes``: 8 words per node {idx_in or 0, val_in, count,
+    idx_out or 0, val_out, sizes, idx_cap bytes, val_cap bytes}.  ``sizes`` is a DEVICE int64[2]
+    with the node's index and value stream bytes; ``idx_in`` None / 0 is a full share.  The words
+    are pointers and constants of a configuration: ``set`` every node and ``upload()`` once."""
+
+    def set(self, j, idx_in, val_in, count, idx_out, val_out, sizes, idx_cap, val_cap):
+        self.host[j] = (self._addr(idx_in), self._addr(val_in), int(count), self._addr(idx_out),
+                        self._addr(val_out), self._addr(sizes), int(idx_cap), int(val_cap))
+
+
+def wire_decode_workspace(m, max_idx_cap, max_count, device, workspace=None):
+    """A uint8 device tensor of ``dpz_wire_decode_nodes_workspace_bytes(m, max_idx_cap,
+    max_count)`` bytes (``workspace`` itself when it is large enough)."""
+    need = max(256, int(_lib.lib().dpz_wire_decode_nodes_workspace_bytes(
+        int(m), int(max_idx_cap), int(max_count))))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+    return workspace
+
+
+def wire_decode_nodes(table, status, precision=0, workspace=None, check_rc=True):
+    """Every node of ``table`` (an uploaded ``WireDecodeTable``) decoded in three launches with
+    nothing read back: the Elias-gamma stream into ``count`` ascending int32 indices (none for a
+    full share) and the block-floating stream of ``precision`` into ``count`` fp32 values, the
+    stream lengths taken from each node's device ``sizes`` words.  ``status`` (device int32, m)
+    gets 0 or the OR of 1 (index stream inconsistent), 2 (another index count than ``count``), 4
+    (bad value stream); such a node's outputs are unwritten or partly written, never overrun, and
+    no other node is affected.  ``workspace``: ``wire_decode_workspace``'s tensor (allocated here
+    when None).  Returns the library's code (raises unless it is DPZ_OK when ``check_rc``)."""
+    _require(table.dev, torch.int64, "table")
+    _require(status, torch.int32, "status")
+    m, dev = table.m, table.dev.device
+    if status.numel() < m:
+        raise ValueError(f"status holds {status.numel()} words, {m} nodes need {m}")
+    h = table.host[:m]
+    coded = h[:, 0] != 0
+    workspace = wire_decode_workspace(m, int(h[coded, 6].max()) if coded.any() else 0,
+                                      int(h[:, 2].max()) if m else 0, dev, workspace)
+    rc = _lib.lib().dpz_wire_decode_nodes(
+        m, _ptr(table.dev), ctypes.c_void_p(table.host.ctypes.data), int(precision), _ptr(status),
+        _ptr(workspace), workspace.numel(), _stream(dev))
+    if check_rc:
+        check(rc, "dpz_wire_decode_nodes")
     return rc
 
 

@@ -23,12 +23,6 @@
 
 namespace dpz {
 
-constexpr int EL_CHUNK = 1024;   // bits per decode chunk
-constexpr int EL_CW = EL_CHUNK / 32;
-constexpr int EL_STAGE = EL_CW + 4;  // staged words per chunk (a code may run 62 bits past)
-constexpr int EL_SUPER = 64;     // chunks per super map
-constexpr int EL_MAX_SUPER = 1024;  // => at most 2^26 code bits per stream
-
 struct ElHdr {
   uint64_t L;       // code bits
   uint64_t nbits;   // L + 128
@@ -167,14 +161,7 @@ __global__ void __launch_bounds__(256) elias_pack_kernel(const int32_t* __restri
 }
 
 // ---------------------------------------------------------------- decode
-__device__ __forceinline__ uint64_t window64(const uint32_t* words, uint64_t rel) {
-  const int wi = (int)(rel >> 5);
-  const uint32_t sh = (uint32_t)(rel & 31);
-  const uint64_t a = ((uint64_t)words[wi] << 32) | words[wi + 1];
-  return sh ? ((a << sh) | (words[wi + 2] >> (32 - sh))) : a;
-}
-
-// wave per chunk: lane o parses from chunk_start + o
+// wave per chunk: lane o parses from chunk_start + o (the geometry and the parse: dpz_wire.h)
 __global__ void __launch_bounds__(256) elias_spec_kernel(const uint32_t* __restrict__ in32,
                                                          uint64_t nwords_in, uint64_t L,
                                                          int64_t nch, uint8_t* exit_tab,
@@ -182,35 +169,12 @@ __global__ void __launch_bounds__(256) elias_spec_kernel(const uint32_t* __restr
   __shared__ uint32_t st[4][EL_STAGE];
   const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t c = (int64_t)blockIdx.x * 4 + wid;
-  const uint64_t wbase = (uint64_t)c * EL_CW;
-  if (lane < EL_STAGE) {
-    const uint64_t w = wbase + lane;
-    st[wid][lane] = w < nwords_in ? __builtin_bswap32(in32[w]) : 0u;
-  }
+  el_stage_chunk(in32, nwords_in, c, true, lane, st[wid]);
   __syncthreads();
   if (c >= nch) return;
-  const uint64_t cstart = (uint64_t)c * EL_CHUNK;
-  const uint64_t cend = (cstart + EL_CHUNK < L) ? cstart + EL_CHUNK : L;
-  uint64_t pos = cstart + lane;
-  uint32_t cnt = 0;
-  uint64_t gsum = 0;
-  uint8_t ex = 0xFF;
-  if (lane < 63 && pos < cend) {
-    bool ok = true;
-    while (pos < cend) {
-      const uint64_t w = window64(st[wid], pos - wbase * 32);
-      const uint32_t z = (uint32_t)__clzll((long long)w);
-      if (w == 0 || z > 31) { ok = false; break; }
-      const uint32_t n = z + 1;
-      const uint64_t gv = (w << z) >> (64 - n);
-      gsum += gv;
-      ++cnt;
-      pos += 2 * z + 1;
-    }
-    if (ok) ex = (uint8_t)(pos - cend);  // < 63
-  } else if (lane < 63 && pos >= cend) {
-    ex = (uint8_t)(pos - cend);  // entry beyond this (last) chunk's end
-  }
+  uint32_t cnt;
+  uint64_t gsum;
+  const uint8_t ex = el_parse_chunk(st[wid], c, L, lane, &cnt, &gsum);
   exit_tab[c * 64 + lane] = ex;
   cnt_tab[c * 64 + lane] = cnt;
   sum_tab[c * 64 + lane] = gsum;
@@ -327,10 +291,7 @@ __global__ void __launch_bounds__(256) elias_write_kernel(const uint32_t* __rest
     if (out32) out32[0] = (int32_t)first;
   }
   const uint64_t wbase = (uint64_t)c * EL_CW;
-  if (lane < EL_STAGE) {
-    const uint64_t w = wbase + lane;
-    st[wid][lane] = w < nwords_in ? __builtin_bswap32(in32[w]) : 0u;
-  }
+  el_stage_chunk(in32, nwords_in, c, true, lane, st[wid]);
   __syncthreads();
   if (c >= nch || hdr->status || lane != 0) return;
   const uint64_t cstart = (uint64_t)c * EL_CHUNK;

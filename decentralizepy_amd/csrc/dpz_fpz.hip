@@ -83,14 +83,6 @@ __global__ void __launch_bounds__(256) fz_pack_kernel(const float* __restrict__ 
   fz_pack_block(x, n, b, prec, mb, lane, stage[wid], out32 + 4 + nblk + 1 + table[b]);
 }
 
-__device__ __forceinline__ uint32_t fz_get(const uint32_t* __restrict__ p, uint32_t pos, int bits) {
-  if (!bits) return 0u;
-  const uint32_t wi = pos >> 5, sh = pos & 31u;
-  uint64_t v = p[wi];
-  if (sh + bits > 32) v |= (uint64_t)p[wi + 1] << 32;
-  return (uint32_t)(v >> sh) & (bits == 32 ? 0xFFFFFFFFu : ((1u << bits) - 1u));
-}
-
 __global__ void __launch_bounds__(256) fz_decode_kernel(const uint32_t* __restrict__ in32,
                                                         int64_t nwords, int64_t n,
                                                         int64_t nblk, int prec, int mb,
@@ -99,49 +91,12 @@ __global__ void __launch_bounds__(256) fz_decode_kernel(const uint32_t* __restri
   const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= nblk) return;
   const int lane = threadIdx.x & 63;
-  const uint32_t* table = in32 + 4;
-  const uint32_t off = table[b], end = table[b + 1];
   const int64_t area = nwords - (4 + nblk + 1);  // words available to the blocks
-  const int64_t base = b * FZ_B;
-  const int cnt = (int)((n - base) < FZ_B ? (n - base) : FZ_B);
-  bool bad = in32[0] != FZ_MAGIC || in32[1] != (uint32_t)n || in32[2] != (uint32_t)prec ||
-             in32[3] != (uint32_t)nblk || off >= end || (int64_t)end > area;
-  uint32_t meta = 0;
-  if (!bad) {
-    meta = in32[4 + nblk + 1 + off];
-    const int w0 = (int)((meta >> 8) & 0xFFu);
-    bad = w0 > 8 || (int)((meta >> 16) & 0xFFu) != mb || end - off != fz_words(cnt, w0, mb) ||
-          (meta >> 24) != 0u;
-  }
-  if (bad) {  // malformed stream: record it, write nothing
-    if (lane == 0) atomicOr(status, 1u);
-    return;
-  }
-  const uint32_t* blk = in32 + 4 + nblk + 1 + off;
-  const uint32_t emin = meta & 0xFFu;
-  const int w = (int)((meta >> 8) & 0xFFu);
-  const uint32_t* ps = blk + 1;
-  const uint32_t* pe = ps + (cnt + 31) / 32;
-  const uint32_t* pm = pe + (cnt * w + 31) / 32;
-  float v[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const uint32_t j = 4u * lane + e;
-    uint32_t u = 0;
-    if ((int)j < cnt) {
-      u = (fz_get(ps, j, 1) << 31) | (((emin + fz_get(pe, j * w, w)) & 0xFFu) << 23) |
-          (fz_get(pm, j * mb, mb) << (23 - mb));
-    }
-    v[e] = __uint_as_float(u);
-  }
-  const int64_t i0 = base + 4 * lane;
-  if (4 * lane + 3 < cnt && aligned16(out)) {
-    *reinterpret_cast<float4*>(out + i0) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (4 * lane + e < cnt) out[i0 + e] = v[e];
-  }
+  const bool hdr = in32[0] == FZ_MAGIC && in32[1] == (uint32_t)n && in32[2] == (uint32_t)prec &&
+                   in32[3] == (uint32_t)nblk;
+  // malformed stream: record it, write nothing
+  if ((!hdr || !fz_decode_block(in32, area, n, nblk, b, mb, lane, out)) && lane == 0)
+    atomicOr(status, 1u);
 }
 
 static inline size_t fz_al256(size_t v) { return (v + 255) & ~size_t(255); }

@@ -3,7 +3,7 @@ gossip_subsampling.py, gossip_epidemic.py, gossip_choco.py, gossip_quant.py, gos
 gossip_topkacc.py, gossip_fft.py) share:
 ``ShardedRound``, the sharding of the nodes over the ranks, ``PackedRowRound``, the packed row
 per node that one all-gather exchanges, and ``WireCoded``, the EliasFpzip wire streams of a round's
-payloads in one batched call."""
+payloads in one batched call and the exchange that carries them."""
 import math
 
 import numpy as np
@@ -68,10 +68,17 @@ class WireCoded:
     * ``_wire_message(q, indices, params)``: the dict the plugin puts on the wire for node q
       (``indices`` None for a full share)."""
 
-    def _init_wire(self, float_precision, partial_ks):
+    def _init_wire(self, float_precision, partial_ks, coded_exchange=False):
         self.float_precision = int(float_precision)
         if self.float_precision < 0:
             raise ValueError("float_precision must be >= 0 (0 or >= 32: lossless)")
+        self._coded = bool(coded_exchange)
+        if self._coded and not self._hip:
+            raise NotImplementedError("coded_exchange codes the rows with the HIP codec only; the "
+                                      "CPU stand-in has no coder")
+        if self._coded and any(k < 2 for k in partial_ks):
+            raise ValueError(f"coded_exchange with a share of k = {min(partial_ks)} indices: the "
+                             "Elias index stream needs two")
         # a one-index share is a valid round (the engines have always run it) but has no Elias
         # stream: the configuration is refused where the wire layer is asked for
         self._wire_low = min((k for k in partial_ks if k < 2), default=None)
@@ -126,6 +133,96 @@ class WireCoded:
         self._wire_sizes = sizes[:m]
         return sizes[:m], status[:m], buf, [(oi if ci else None, ov) for oi, ci, ov, _ in caps]
 
+    # ---- the coded exchange: rows of equal k, PackedRowRound's layout ---------------------------
+    def _init_coded(self, k, n, idx_word, val_word):
+        """After ``_alloc_rows``: the coded rows and the two static tables of an engine whose raw
+        row holds k ascending indices below n from int32 word ``idx_word`` and k values from
+        ``val_word``.  A coded row is ``[count int64, status, 0 | index bytes int64, value bytes
+        int64 | index slot | value slot]`` with slots of up4(``dpz_elias_bound_bytes(k, n)``) and
+        ``dpz_fpz_bound_bytes(k, float_precision)`` bytes.  ``csend`` holds this rank's, ``crecv``
+        every rank's after the all-gather (``csend`` itself without collectives); the decode
+        writes raw-layout rows into ``recv``, which the folds then read (``rows``)."""
+        from . import codec
+        H, i32 = PackedRowRound.HEADER, dict(dtype=torch.int32, device=self.device)
+        ci, cv = up4(codec.elias_bound_bytes(k, n)), codec.fpz_bound_bytes(k, self.float_precision)
+        oi, ov = 4 * (H + 4), 4 * (H + 4) + ci
+        self._cslots = (oi, ov)
+        self.csend = torch.zeros(self.per, up4(H + 4 + (ci + cv) // 4), **i32)
+        self.crecv = torch.zeros(self.per * self.world, self.csend.shape[1],
+                                 **i32) if self.coll else self.csend
+        self.csend[:, :2] = torch.tensor([k], dtype=torch.int64).view(torch.int32).to(self.device)
+        if self.recv is None:
+            self.recv = torch.zeros(self.per * self.world, self.row_words, **i32)
+        m = self.m
+        self._enc_tab = codec.WireNodesTable(m, self.device)
+        for j in range(m):
+            raw, c = self.send[j].data_ptr(), self.csend[j].data_ptr()
+            self._enc_tab.set(j, raw + 4 * idx_word, raw + 4 * val_word, k, c + oi, c + ov, ci, cv)
+        self._enc_tab.upload()
+        self._enc_sizes = torch.zeros(max(1, m), 2, dtype=torch.int64, device=self.device)
+        self._enc_status = torch.zeros(max(1, m), **i32)
+        self._enc_ws = codec.wire_nodes_workspace(max(1, m), k, self.device)
+        # the static set of nodes this rank's neighbourhoods fold
+        nodes = sorted({q for i in range(self.lo, self.hi) for q in self.adj[i]})
+        self._dec_tab = codec.WireDecodeTable(len(nodes), self.device)
+        for j, q in enumerate(nodes):
+            raw, c = self.recv[q].data_ptr(), self.crecv[q].data_ptr()
+            self._dec_tab.set(j, c + oi, c + ov, k, raw + 4 * idx_word, raw + 4 * val_word,
+                              c + 4 * H, ci, cv)
+        self._dec_tab.upload()
+        self._dec_status = torch.zeros(max(1, len(nodes)), **i32)
+        self._dec_all = nodes == list(range(self.per * self.world))
+        self._dec_nodes = torch.tensor(nodes, dtype=torch.int64, device=self.device)
+        self._dec_ws = codec.wire_decode_workspace(max(1, len(nodes)), ci, k, self.device)
+
+    def _coded_encode(self):
+        """After the selection: ONE ``wire_encode_nodes`` call from the raw rows into the coded
+        rows' slots; the stream lengths go into the rows' header words and the coder's status is
+        ORed into the rows' status words."""
+        from . import codec
+        m, H = self.m, PackedRowRound.HEADER
+        if not m:
+            return
+        codec.wire_encode_nodes(self._enc_tab, self._enc_sizes, self._enc_status,
+                                self.float_precision, self._enc_ws)
+        self.csend[:m, H:H + 4].copy_(self._enc_sizes[:m].view(torch.int32))
+        torch.bitwise_or(self.send[:m, 2], self._enc_status[:m], out=self.csend[:m, 2])
+
+    @property
+    def rows(self):
+        """The rows the folds read: the decoded ones with a coded exchange."""
+        return self.recv if self._coded else super().rows
+
+    def exchange(self):
+        """With ``coded_exchange``: ONE all-gather of the coded rows (in place with one rank and no
+        group), then ONE ``wire_decode_nodes`` call into the raw-layout receive buffer; the decode
+        status is ORed into the guard words of the guarded fold."""
+        if not self._coded:
+            return super().exchange()
+        from . import codec
+        if self.coll:
+            self.all_gather(self.crecv, self.csend)
+        if not self._dec_tab.m:
+            return self.guard.copy_(self.crecv[:, 2])
+        codec.wire_decode_nodes(self._dec_tab, self._dec_status, self.float_precision,
+                                self._dec_ws)
+        if self._dec_all:
+            torch.bitwise_or(self.crecv[:, 2], self._dec_status, out=self.guard)
+        else:
+            self.guard.copy_(self.crecv[:, 2])
+            self.guard[self._dec_nodes] |= self._dec_status
+
+    def _coded_stream(self, q):
+        """Owned node q's coded row on the host, sliced into (indices, params).  Blocks."""
+        H = PackedRowRound.HEADER
+        row = self.csend[q - self.lo].cpu().numpy().view(np.uint8)
+        nb_i, nb_v = row[4 * H:4 * H + 16].view(np.int64).tolist()
+        if row[8:12].view(np.int32)[0]:
+            raise RuntimeError(f"wire streams of node {q} refused (status "
+                               f"{int(row[8:12].view(np.int32)[0])})")
+        oi, ov = self._cslots
+        return row[oi:oi + nb_i].copy(), row[ov:ov + nb_v].copy()
+
     def wire_bytes(self):
         """Device int64 ``(m, 2)``: the bytes of the index stream (0 for a full share) and of the
         value stream of every owned node's payload of the last ``encode()`` / ``step()``, as
@@ -133,6 +230,11 @@ class WireCoded:
         call of two launches; nothing synchronises with the host.  The pickle framing that the
         reference's ``TCP.encrypt`` adds is not counted: it is made on the host and is the same
         for every message of a configuration."""
+        if self._coded:  # the coded rows' header words: nothing is launched
+            if not self._wire_encoded:
+                raise RuntimeError("no round has been encoded yet")
+            H = PackedRowRound.HEADER
+            return self.csend[:self.m, H:H + 4].view(torch.int64)
         if self._wire_sizes is None:
             self._wire_call(False)
         return self._wire_sizes
@@ -146,6 +248,10 @@ class WireCoded:
         the streams to the host (one synchronisation); later calls read that cache."""
         if not self.lo <= q < self.hi:
             raise ValueError(f"node {q} is not one of this rank's nodes [{self.lo}, {self.hi})")
+        if self._coded:  # a slice of the coded row that was exchanged
+            if not self._wire_encoded:
+                raise RuntimeError("no round has been encoded yet")
+            return self._wire_message(q, *self._coded_stream(q))
         if self._wire_streams is None:
             sizes, status, buf, offs = self._wire_call(True)
             host = torch.empty(buf.numel(), dtype=torch.uint8, pin_memory=True)

@@ -20,7 +20,11 @@ resident in HBM and shards the nodes over the ranks like the other engines.  A r
 ``dpz_topkacc_encode_nodes`` launch set over the owned nodes, ONE ``all_gather_into_tensor`` of a
 packed row per node, the batched one-launch fold with the payload pointers pointing into the
 packed rows, in mode "avg" ONE ``dpz_topkacc_post_nodes`` launch, and the swap of ``x0`` with the
-fold's output.  In mode "avg" the encode's key vector goes into the fold's output row, which is
+fold's output.  With ``coded_exchange=True`` the all-gather carries the rows as the EliasFpzip wire
+streams instead (``gossip_round.WireCoded``): one ``dpz_wire_encode_nodes`` call after the
+selection, one ``dpz_wire_decode_nodes`` call after the all-gather, and the fold reads what the
+receivers decoded, so ``float_precision = p`` folds values truncated to their top p bits as the
+reference's ``EliasFpzipLossy`` round does.  In mode "avg" the encode's key vector goes into the fold's output row, which is
 free until the fold: no extra allocation.  Nothing synchronises with the host inside ``step()``.
 
 Ties at the k-th key go to the lowest indices (``torch.topk``'s order is implementation-defined).
@@ -46,7 +50,7 @@ class TopKAccRound(WireCoded, PackedRowRound):
 
     def __init__(self, adj, x_init, alpha, accumulate_averaging_changes=False, metadata_cap=1.0,
                  rank=0, world=1, group=None, device=None, encode=None, fold=None, post=None,
-                 float_precision=0, **unknown):
+                 float_precision=0, coded_exchange=False, **unknown):
         """adj: adjacency sets of all nodes; x_init: (hi - lo, N) fp32, this rank's nodes' models.
         ``encode(x, x0, acc, counter, k, avg) -> (idx, vals)`` (one node, in place on acc and
         counter), ``fold(local, payloads, weights, w_self, out)`` (``GossipRound``'s) and
@@ -54,8 +58,8 @@ class TopKAccRound(WireCoded, PackedRowRound):
         if unknown:
             raise ValueError(
                 f"unknown arguments {sorted(unknown)}: TopKAccRound offers neither the peer nor the "
-                "reduce-scatter exchange nor compressed payloads; use gossip.GossipRound for plain "
-                "top-k with those exchanges")
+                "reduce-scatter exchange; use gossip.GossipRound for plain top-k with those "
+                "exchanges")
         injected = [f is not None for f in (encode, fold, post)]
         if any(injected) != all(injected):
             raise ValueError("encode, fold and post are injected together")
@@ -71,7 +75,7 @@ class TopKAccRound(WireCoded, PackedRowRound):
                              "use gossip_subsampling.SubSamplingRound for tiny random shares")
         self._hip = not any(injected)
         self._encode, self._fold, self._post = encode, fold, post
-        self._init_wire(float_precision, [self.k])
+        self._init_wire(float_precision, [self.k], coded_exchange)
         self.cap = up4(self.k)
         stride = up4(N)  # every row 16-byte aligned
         self._state = torch.zeros(4, max(1, m), stride, dtype=torch.float32, device=self.device)
@@ -85,6 +89,8 @@ class TopKAccRound(WireCoded, PackedRowRound):
                                    device=self.device)[:m, :N]
         # a packed row: [count = k (int64), status = 0, 0 | cap idx | cap vals]
         self._alloc_rows(HEADER + 2 * self.cap)
+        if self._coded:
+            self._init_coded(self.k, N, HEADER, HEADER + self.cap)
         self.weights = [mh_weights(adj, i) for i in range(self.lo, self.hi)]
         self._tabs = {}
         self._fold_tab = self._ws = self._dws = None
@@ -96,7 +102,8 @@ class TopKAccRound(WireCoded, PackedRowRound):
 
     def payload(self, q):
         """``(idx, vals)`` of node q's payload of its last encode (an owned node; any node after
-        an all-gather)."""
+        an all-gather).  With ``coded_exchange``: what the receivers fold, the decoded payload of
+        the last exchange (an owned node's own selection stays in ``send``)."""
         return self._pay(self._row(q))
 
     # ---- the wire layer's hooks (gossip_round.WireCoded) -----------------------------------------
@@ -170,6 +177,8 @@ class TopKAccRound(WireCoded, PackedRowRound):
                 mode = codec.DPZ_ACC_ADD if self.avg else codec.DPZ_ACC_ACCUMULATE
                 self._ws = codec.topkacc_encode_nodes(self._tables()["node"], self.N, self.k,
                                                       mode, self._ws)
+            if self._coded:
+                self._coded_encode()
             return
         for j in range(self.m):
             self._write_row(self.send[j], *self._encode(self.x[j], self.x0[j], self.acc[j],
@@ -214,7 +223,8 @@ class TopKAccRound(WireCoded, PackedRowRound):
             self._post(self.acc[j], self.out[j], self.x0[j])
 
     def step(self, mark=None):
-        """One round: the encode launch set, one all-gather (with a process group), the batched
+        """One round: the encode launch set (with ``coded_exchange`` followed by the wire coder's),
+        one all-gather (with a process group; then the wire decoder's launch set), the batched
         fold, in mode "avg" one post-step launch, and the swap that makes the averaged model the
         next round's ``x0``.  Nothing synchronises with the host.  ``mark(leg)`` is called after
         each leg is enqueued (tools/bench_topkacc_round.py records an event)."""

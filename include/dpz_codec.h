@@ -1255,6 +1255,49 @@ int dpz_wire_encode_nodes(int m, const void* table, const void* host_table, int 
                           int64_t* sizes, uint32_t* status, void* ws, size_t ws_bytes,
                           dpz_stream_t stream);
 
+/* ---- The wire streams of many nodes decoded at once (csrc/dpz_wire_decode_nodes.hip) -------------
+ * dpz_wire_decode_nodes: for each of m nodes the Elias-gamma index stream into count ascending
+ * int32 indices and the block-floating value stream into count fp32 values (the formats of
+ * dpz_elias_encode and dpz_fpz_encode), in at most THREE launches whatever m is (speculate +
+ * values, a 4-wave resolve per node, write), with no memset, nothing read back and no host
+ * synchronisation.  table is a DEVICE array of m entries of 8 64-bit words {idx_in or 0, val_in,
+ * count, idx_out, val_out, sizes, idx_cap bytes, val_cap bytes}; host_table is its HOST copy, on
+ * which every check is made before anything is enqueued.  The table holds only pointers and
+ * constants of a configuration: upload it once.  Per node:
+ *   sizes      DEVICE int64[2]: the index and the value stream's bytes (a row of
+ *              dpz_wire_encode_nodes' sizes, or two words of a received row).  The host never
+ *              reads them; nbits and first come from the index stream's trailer, on the device.
+ *   idx_in     0: a full share, no index stream, idx_out must be 0 too.  Otherwise count >= 2.
+ *   every read of a stream stays below its cap, every write below count entries.
+ *   status[j] (DEVICE uint32, written for every node): 0, or the OR of
+ *     1  the index stream is inconsistent: sizes[0] below 16 or above idx_cap, the trailer's
+ *        nbits below 128 or beyond the bytes, a code of more than 63 bits, the path of codes
+ *        not ending at nbits - 128;
+ *     2  the index stream is well formed but holds another number of indices than count;
+ *     4  the value stream is bad: sizes[1] above val_cap, no multiple of 4 or too short for its
+ *        table, a header that is not {magic, count, precision, blocks}, a bad table entry or
+ *        block meta word.
+ *   With 1 or 2 no index is written; with 4 the values of the good blocks may be.  Another
+ *   node's outputs never depend on it.
+ * A stream may hold at most 2^26 code bits; that is decided from idx_cap.  The launches are
+ * timed as "elias_spec", "elias_resolve" and "elias_write".  ws:
+ * dpz_wire_decode_nodes_workspace_bytes(m, largest idx_cap of a node with idx_in, largest count)
+ * DEVICE bytes (0 for m < 1, a negative cap, a count outside [0, 2^30] or a cap above the
+ * 2^26-bit limit), 8-byte aligned, any content.
+ * Before anything is enqueued: DPZ_ERR_ARG for m < 1, a null or misaligned table, status or
+ * workspace pointer (8, 4, 8 bytes), a null host table, a count outside [0, 2^30], a null val_in
+ * or sizes, a null val_out with count > 0, idx_in with count < 2 or without idx_out, idx_out
+ * without idx_in, a stream or list pointer that is not 4-byte aligned, sizes not 8-byte aligned,
+ * a negative cap; DPZ_ERR_UNSUPPORTED for a negative precision, m > 65535 and an idx_cap of more
+ * than 1024 super maps (2^26 bits); DPZ_ERR_WORKSPACE for a null or short workspace.
+ * dpz_fpz_bound_bytes (host only): the largest value stream of n values at a precision,
+ * 4 (4 + nblk + 1 + nblk (73 + 8 mb)) with mb the precision's mantissa bits: dpz_fpz_max_bytes(n)
+ * when lossless, smaller otherwise; 0 for a negative n or precision.                             */
+int64_t dpz_fpz_bound_bytes(int64_t n, int precision);
+size_t dpz_wire_decode_nodes_workspace_bytes(int m, int64_t max_idx_cap, int64_t max_count);
+int dpz_wire_decode_nodes(int m, const void* table, const void* host_table, int precision,
+                          uint32_t* status, void* ws, size_t ws_bytes, dpz_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

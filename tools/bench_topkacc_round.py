@@ -35,7 +35,15 @@ the ENGINE's algorithmic bytes per node, k = round(alpha N):
 ``copy_tb_per_s`` is a device-to-device copy of 1 GiB timed in the same process.  Prints one JSON
 line per (alpha, mode).
 
+``--coded`` compares two engines instead of the engine and the baseline: ``TopKAccRound`` as above
+("uncoded") and ``TopKAccRound(coded_exchange=True, float_precision=--precision)`` ("coded"), whose
+encode leg ends with ONE ``dpz_wire_encode_nodes`` call and whose exchange leg is ONE
+``dpz_wire_decode_nodes`` call (on one rank no all-gather runs, so what the smaller rows save on
+the wire is NOT measured; the row sizes are reported from the slot bounds).  At precision 0 the
+two states must stay equal in every bit.
+
     python tools/bench_topkacc_round.py [--n 11000000] [--alphas 0.01,0.1] [--modes acc,avg] [--shape sw96]
+                                        [--coded] [--precision 0]
 """
 import argparse
 import json
@@ -216,6 +224,62 @@ def run_config(args, adj, dev, alpha, avg, copy):
         raise SystemExit("the engine's and the baseline's states differ")
 
 
+def run_coded(args, adj, dev, alpha, avg):
+    m, n = len(adj), args.n
+    gen = torch.Generator(device=dev).manual_seed(1)
+    x0 = torch.randn(m, n, device=dev, generator=gen)
+    noise = torch.randn(n, device=dev, generator=gen)
+    variants = {"uncoded": TopKAccRound(adj, x0, alpha, accumulate_averaging_changes=avg),
+                "coded": TopKAccRound(adj, x0, alpha, accumulate_averaging_changes=avg,
+                                      coded_exchange=True, float_precision=args.precision)}
+    del x0
+    runs = {name: {} for name in variants}
+    r = 0
+    for run in range(-1, args.runs):  # run -1: the warm-up rounds
+        legs = {name: {} for name in variants}
+        for _ in range(args.warmup + 2 if run < 0 else args.rounds):
+            for obj in variants.values():
+                for u in range(m):
+                    obj.x[u].add_(torch.roll(noise, 7919 * (u + 1) + r), alpha=0.01)
+            for name, obj in variants.items():
+                for leg, ms in timed_round(obj).items():
+                    legs[name].setdefault(leg, []).append(ms)
+            r += 1
+        if run >= 0:
+            for name in variants:
+                for leg, ts in legs[name].items():
+                    runs[name].setdefault(leg, []).append(float(np.median(ts)))
+    torch.cuda.synchronize()
+    unc, cod = variants["uncoded"], variants["coded"]
+    same = eq(unc.x0, cod.x0) and eq(unc.acc, cod.acc) and torch.equal(unc.counter, cod.counter)
+    sizes = cod.wire_bytes().sum(0).tolist()
+    with codec.KernelTimer() as kt:  # five more rounds of the coded engine: its launches alone
+        for i in range(5):
+            for u in range(m):
+                cod.x[u].add_(torch.roll(noise, 7919 * (u + 1) + r + i), alpha=0.01)
+            cod.step()
+        torch.cuda.synchronize()
+    launch_ms = {name: round(ms / cnt, 4) for name, (ms, cnt) in sorted(kt.result.items())}
+    res = {"device": torch.cuda.get_device_name(0), "bench": "coded", "nodes": m, "n": n,
+           "alpha": alpha, "mode": "avg" if avg else "acc", "k": unc.k,
+           "precision": args.precision, "rounds": args.rounds, "runs": args.runs,
+           "warmup": args.warmup + 2, "results_equal": bool(same),
+           "guard_clean": not bool(cod.guard.any()),
+           "row_bytes": {"raw": 4 * unc.row_words, "coded_bound": 4 * cod.csend.shape[1],
+                         "coded_used_mean": round((sum(sizes) / m) + 32, 1)},
+           "all_gather_saving": "not measured (one rank)", "coded_launch_ms": launch_ms}
+    for name in variants:
+        res[name] = {leg: {"min_ms": round(min(t), 4), "max_ms": round(max(t), 4)}
+                     for leg, t in runs[name].items()}
+        res[name]["round_ms"] = [round(sum(res[name][leg][key] for leg in runs[name]), 4)
+                                 for key in ("min_ms", "max_ms")]
+    u, c = res["uncoded"]["round_ms"], res["coded"]["round_ms"]
+    res["coded_over_uncoded"] = [round(c[0] / u[1], 3), round(c[1] / u[0], 3)]
+    print(json.dumps(res), flush=True)
+    if args.precision == 0 and not same:
+        raise SystemExit("the coded and the uncoded engine's states differ")
+
+
 SHAPES = {"sw96": ("96_nodes_smallworld.edges", 89_834)}
 
 
@@ -233,6 +297,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=50)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--coded", action="store_true",
+                    help="time TopKAccRound with coded_exchange against the uncoded engine")
+    ap.add_argument("--precision", type=int, default=0, help="float_precision of --coded")
     args = ap.parse_args()
     if args.shape:
         args.edges, args.n = os.path.join(ROOT, "tests", "golden", SHAPES[args.shape][0]), \
@@ -256,7 +323,10 @@ def main():
         for mode in args.modes.split(","):
             if mode not in ("acc", "avg"):
                 raise SystemExit(f"unknown mode {mode}")
-            run_config(args, adj, dev, alpha, mode == "avg", copy)
+            if args.coded:
+                run_coded(args, adj, dev, alpha, mode == "avg")
+            else:
+                run_config(args, adj, dev, alpha, mode == "avg", copy)
             torch.cuda.empty_cache()
 
 
