@@ -269,12 +269,19 @@ SIGNATURES = {
     "dpz_topkacc_encode_workspace_bytes": (_size, [_int, _i64]),
     "dpz_topkacc_encode_nodes": (_int, [_int, _c_void_p, _i64, _i64, _int, _c_void_p, _size,
                                         _c_void_p]),
+    "dpz_topkacc_encode_window_workspace_bytes": (_size, [_int, _i64, _i64]),
+    "dpz_topkacc_encode_nodes_window": (_int, [_int, _c_void_p, _i64, _i64, _int, _c_void_p,
+                                               _size, _c_void_p]),
     "dpz_topkacc_post_nodes": (_int, [_int, _c_void_p, _i64, _c_void_p]),
     "dpz_dwt_sym2_nodes": (_int, [_int, _c_void_p, _c_void_p, _i64, _int, _int, _c_void_p]),
     "dpz_idwt_sym2_nodes": (_int, [_int, _c_void_p, _c_void_p, _i64, _int, _c_void_p]),
     "dpz_jwins_chunk_elems": (_i64, []),
     "dpz_jwins_encode_workspace_bytes": (_size, [_int, _i64]),
     "dpz_jwins_encode_nodes": (_int, [_int, _c_void_p, _i64, _c_void_p, _size, _c_void_p]),
+    "dpz_jwins_window_slots": (_int, []),
+    "dpz_jwins_encode_window_workspace_bytes": (_size, [_int, _i64, _i64]),
+    "dpz_jwins_encode_nodes_window": (_int, [_int, _c_void_p, _i64, _i64, _c_void_p, _size,
+                                             _c_void_p]),
     "dpz_wvgen_tile_width": (_i64, []),
     "dpz_wavelet_generic_nodes_workspace_bytes": (_size, [_int, _i64, _int, _int]),
     "dpz_dwt_generic_nodes": (_int, [_int, _c_void_p, _c_void_p, _i64, _int, _c_void_p, _int, _int,

@@ -35,7 +35,8 @@ __all__ = ["DPZ_ACC_NONE", "DPZ_ACC_ACCUMULATE", "DPZ_ACC_ADD", "DPZ_EW_SUB", "D
            "stc_row_words", "stc_node_table", "stc_encode_nodes", "StcFoldTable",
            "stc_server_fold", "stc_apply_table", "stc_apply_nodes", "topkacc_chunk_elems",
            "topkacc_row_words", "topkacc_node_table", "topkacc_encode_nodes",
-           "topkacc_post_nodes", "DwtNodesTable", "IdwtNodesTable", "dwt_sym2_nodes",
+           "topkacc_post_nodes", "topkacc_encode_nodes_window", "jwins_encode_nodes_window",
+           "window_status", "DwtNodesTable", "IdwtNodesTable", "dwt_sym2_nodes",
            "idwt_sym2_nodes", "jwins_chunk_elems", "JwinsEncodeTable", "jwins_encode_nodes",
            "wavelet_nodes_tile_width", "wavelet_nodes_workspace", "dwt_generic_nodes",
            "idwt_generic_nodes", "elias_bound_bytes", "WireNodesTable", "wire_nodes_workspace",
@@ -1716,6 +1717,36 @@ def topkacc_encode_nodes(table, n, k, mode, workspace=None):
     return _encode_nodes("topkacc", table, table.shape[0], int(n), (int(k), int(mode)), workspace)
 
 
+def _window_nodes(name, table, m, n, args, kcap, workspace):
+    """``dpz_<name>_encode_nodes_window``: the workspace is zeroed where it is allocated (no prior
+    yet) and must come back for the next round, since it holds the priors."""
+    lib = _lib.lib()
+    need = int(getattr(lib, f"dpz_{name}_encode_window_workspace_bytes")(m, n, kcap))
+    if workspace is None:
+        workspace = torch.zeros(max(need, 256), dtype=torch.uint8, device=table.device)
+    rc = getattr(lib, f"dpz_{name}_encode_nodes_window")(
+        m, _ptr(table), n, *args, _ptr(workspace), workspace.numel(), _stream(table.device))
+    check(rc, f"dpz_{name}_encode_nodes_window")
+    return workspace
+
+
+def window_status(workspace, m):
+    """The per-node status words of the last windowed encode on ``workspace``, a DEVICE int32 view
+    of length m: 0 = exact (no prior for the node's k), 1 = window hit, 2 = miss, then exact."""
+    return workspace[:4 * m].view(torch.int32)
+
+
+def topkacc_encode_nodes_window(table, n, k, mode, workspace=None):
+    """``topkacc_encode_nodes`` with the windowed one-read selection: the same rows, acc and
+    counter bit for bit.  A node whose last threshold still brackets this round's is selected
+    from one stream over its operands; every other node runs the exact launch set, on the device.
+    ``workspace`` holds the priors: pass back what the last call returned (None: allocated and
+    zeroed here, a first round).  ``window_status`` reads the per-node outcome."""
+    _require(table, torch.int64, "table")
+    return _window_nodes("topkacc", table, table.shape[0], int(n), (int(k), int(mode)), int(k),
+                         workspace)
+
+
 def topkacc_post_nodes(table, n):
     """PartialModel's accumulating ``_post_step`` of every node of ``table``
     (``topkacc_node_table``) in one launch: ``acc += x - x0``, x the averaged model and x0 the model
@@ -1855,8 +1886,8 @@ class JwinsEncodeTable:
             return 0
         return t.data_ptr() if isinstance(t, torch.Tensor) else int(t)
 
-    def set(self, j, k, idx_out, val_out):
-        self.host[j, 4:] = (self._addr(idx_out), self._addr(val_out), int(k), 0)
+    def set(self, j, k, idx_out, val_out, slot=0):
+        self.host[j, 4:] = (self._addr(idx_out), self._addr(val_out), int(k), int(slot))
 
     def upload(self):
         src = torch.from_numpy(self.host.view(np.int64))
@@ -1884,6 +1915,25 @@ def jwins_encode_nodes(table, n, workspace=None):
         raise ValueError("a node table with a null row: c, acc and vals_src of every node, "
                          "idx_out and val_out of every node with k >= 1")
     return _encode_nodes("jwins", table.dev, m, n, (), workspace)
+
+
+def jwins_encode_nodes_window(table, n, kmax, workspace=None):
+    """``jwins_encode_nodes`` with the windowed one-read selection: the same outputs bit for bit.
+    Word 7 of a node's entry (``JwinsEncodeTable.set(..., slot=)``) names the prior slot of its k;
+    ``kmax``, the largest k a node may draw, sizes the candidate lists.  ``workspace`` holds the
+    priors: pass back what the last call returned (None: allocated and zeroed here)."""
+    _require(table.dev, torch.int64, "table")
+    m, n = table.m, int(n)
+    ks = table.host[:m, 6]
+    if m and int(ks.max()) > int(kmax):
+        raise ValueError(f"a node's k = {int(ks.max())} exceeds kmax = {int(kmax)}")
+    if m and int(table.host[:m, 7].max()) >= int(_lib.lib().dpz_jwins_window_slots()):
+        raise ValueError("a prior slot past dpz_jwins_window_slots()")
+    part = ks > 0
+    if (table.host[:m, :3] == 0).any() or (table.host[:m, 4:6][part] == 0).any():
+        raise ValueError("a node table with a null row: c, acc and vals_src of every node, "
+                         "idx_out and val_out of every node with k >= 1")
+    return _window_nodes("jwins", table.dev, m, n, (int(kmax),), int(kmax), workspace)
 
 
 def elias_bound_bytes(k, n):

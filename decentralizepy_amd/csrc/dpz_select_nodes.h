@@ -61,12 +61,31 @@ static inline NodeWs node_ws(int64_t n) {
   return L;
 }
 
+// What the windowed selection (dpz_select_window_nodes.h) keeps per node across calls, and what
+// the kernels here need of it in their WIN form: a node whose status word is 1 was selected
+// by the window launches and leaves every kernel at once, as an idle node does; the scan leaves
+// its T as the prior of the node's k slot.
+constexpr int WIN_SLOTS = 16;
+struct WinCtrl {  // a node's control block; the priors outlive a call
+  uint32_t lo, hi;  // this call's window, both ends inside; lo > hi: none
+  uint32_t T, ties;
+  uint32_t pad[28];
+  uint32_t prior_T[WIN_SLOTS], prior_k[WIN_SLOTS];  // prior_T == 0: none
+};
+static_assert(sizeof(WinCtrl) == 256, "ctrl size");
+struct SelectWin {
+  const uint32_t* status;  // m words
+  char* ctrl;              // node 0's WinCtrl
+  size_t stride;           // bytes from a node's to the next
+};
+
 template <class A>
 struct SelectArgs {
   A p;  // the engine's
   char* ws;
   NodeWs L;
   int64_t n;
+  SelectWin win;  // WIN kernels only
 };
 
 __device__ __forceinline__ int count4(int64_t i0, int64_t n) {
@@ -115,12 +134,15 @@ __device__ __forceinline__ void select_rule(const TopkCtrl* ctrl, uint32_t& T, u
   }
 }
 
-template <class P, int PASS>
+template <class P, int PASS, bool WIN = false>
 __global__ void __launch_bounds__(256) select_hist_kernel(const SelectArgs<typename P::Args> a) {
   constexpr int NB = (PASS == 1) ? 2048 : 1024;
   constexpr int HOFF = (PASS == 0) ? 0 : (PASS == 1 ? 1024 : 3072);
   __shared__ uint32_t h[NB];
   const typename P::Node nd = a.p.tab[blockIdx.y];
+  if constexpr (WIN) {
+    if (a.win.status[blockIdx.y] == 1) return;  // uniform over the block
+  }
   if constexpr (P::kIdleNodes) {
     if (P::idle(nd)) {  // uniform over the block, before any barrier
       if (PASS == 0) P::idle_share(nd, a.n);
@@ -162,7 +184,7 @@ __global__ void __launch_bounds__(256) select_hist_kernel(const SelectArgs<typen
 }
 
 // One block of 1024 threads per node: the digit that holds the krem-th largest key.
-template <class P, int PASS>
+template <class P, int PASS, bool WIN = false>
 __global__ void __launch_bounds__(1024)
     select_resolve_kernel(const SelectArgs<typename P::Args> a) {
   constexpr int NB = (PASS == 1) ? 2048 : 1024;
@@ -171,6 +193,9 @@ __global__ void __launch_bounds__(1024)
   constexpr int PER = NB / 1024;
   __shared__ uint32_t wsum[16];
   const typename P::Node nd = a.p.tab[blockIdx.x];
+  if constexpr (WIN) {
+    if (a.win.status[blockIdx.x] == 1) return;  // uniform over the block
+  }
   if constexpr (P::kIdleNodes) {
     if (P::idle(nd)) return;  // uniform over the block
   }
@@ -200,10 +225,13 @@ __global__ void __launch_bounds__(1024)
   }
 }
 
-template <class P>
+template <class P, bool WIN = false>
 __global__ void __launch_bounds__(256) select_count_kernel(const SelectArgs<typename P::Args> a) {
   __shared__ uint32_t wsum[16];
   const typename P::Node nd = a.p.tab[blockIdx.y];
+  if constexpr (WIN) {
+    if (a.win.status[blockIdx.y] == 1) return;  // uniform over the block
+  }
   if constexpr (P::kIdleNodes) {
     if (P::idle(nd)) return;  // uniform over the block
   }
@@ -230,10 +258,13 @@ __global__ void __launch_bounds__(256) select_count_kernel(const SelectArgs<type
 
 // One block of 1024 threads per node: every chunk's output offset and the ties before it (its
 // share of the allotment follows: ties go to the lowest indices), and the engine's row header.
-template <class P>
+template <class P, bool WIN = false>
 __global__ void __launch_bounds__(1024) select_scan_kernel(const SelectArgs<typename P::Args> a) {
   __shared__ uint64_t wsum[16];
   const typename P::Node nd = a.p.tab[blockIdx.x];
+  if constexpr (WIN) {
+    if (a.win.status[blockIdx.x] == 1) return;  // uniform over the block
+  }
   if constexpr (P::kIdleNodes) {
     if (P::idle(nd)) return;  // uniform over the block
   }
@@ -266,12 +297,23 @@ __global__ void __launch_bounds__(1024) select_scan_kernel(const SelectArgs<type
   if constexpr (P::kHeader) {
     if (threadIdx.x == 0) P::header(nd, a.p, carry_off);
   }
+  if constexpr (WIN) {  // the exact T is the next call's prior for this k
+    if (threadIdx.x == 0) {
+      WinCtrl* wc = reinterpret_cast<WinCtrl*>(a.win.ctrl + (size_t)blockIdx.x * a.win.stride);
+      const uint32_t slot = P::kslot(nd, a.p) & (WIN_SLOTS - 1);
+      wc->prior_T[slot] = reinterpret_cast<const TopkCtrl*>(ws + a.L.ctrl)->prefix;
+      wc->prior_k[slot] = P::k(nd, a.p, a.n);
+    }
+  }
 }
 
-template <class P>
+template <class P, bool WIN = false>
 __global__ void __launch_bounds__(256) select_write_kernel(const SelectArgs<typename P::Args> a) {
   __shared__ uint32_t wsum[16];
   const typename P::Node nd = a.p.tab[blockIdx.y];
+  if constexpr (WIN) {
+    if (a.win.status[blockIdx.y] == 1) return;  // uniform over the block
+  }
   if constexpr (P::kIdleNodes) {
     if (P::idle(nd)) return;  // uniform over the block
   }
@@ -321,27 +363,29 @@ __global__ void __launch_bounds__(256) select_write_kernel(const SelectArgs<type
 }
 
 // The selection of m nodes on the stream: ws holds m * node_ws(n).total bytes.
-template <class P, class First = P>
-int select_nodes(int m, const typename P::Args& args, int64_t n, void* ws, hipStream_t st) {
+template <class P, class First = P, bool WIN = false>
+int select_nodes(int m, const typename P::Args& args, int64_t n, void* ws, hipStream_t st,
+                 const SelectWin& win = SelectWin()) {
   SelectArgs<typename P::Args> a;
   a.p = args;
   a.ws = static_cast<char*>(ws);
   a.L = node_ws(n);
   a.n = n;
+  a.win = win;
   // every node's control block and histograms (the chunk arrays are written before they are read)
   DPZ_HIP_TRY(hipMemsetAsync(ws, 0, (size_t)m * a.L.total, st));
   const int64_t groups = (n + 3) / 4;
   const unsigned hb = (unsigned)std::min<int64_t>(EX_HIST_BLOCKS, (groups + 255) / 256);
   const dim3 hgrid(hb, (unsigned)m), cgrid((unsigned)a.L.nblk, (unsigned)m);
-  DPZ_TIMED(DPZ_KT_EXACT_HIST, st, select_hist_kernel<First, 0><<<hgrid, 256, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_RESOLVE, st, select_resolve_kernel<P, 0><<<m, 1024, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_HIST, st, select_hist_kernel<P, 1><<<hgrid, 256, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_RESOLVE, st, select_resolve_kernel<P, 1><<<m, 1024, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_HIST, st, select_hist_kernel<P, 2><<<hgrid, 256, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_RESOLVE, st, select_resolve_kernel<P, 2><<<m, 1024, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_COUNT, st, select_count_kernel<P><<<cgrid, 256, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_SCAN, st, select_scan_kernel<P><<<m, 1024, 0, st>>>(a));
-  DPZ_TIMED(DPZ_KT_EXACT_WRITE, st, select_write_kernel<P><<<cgrid, 256, 0, st>>>(a));
+  DPZ_TIMED(DPZ_KT_EXACT_HIST, st, select_hist_kernel<First, 0, WIN><<<hgrid, 256, 0, st>>>(a));
+  DPZ_TIMED(DPZ_KT_EXACT_RESOLVE, st, select_resolve_kernel<P, 0, WIN><<<m, 1024, 0, st>>>(a));
+  DPZ_TIMED(DPZ_KT_EXACT_HIST, st, select_hist_kernel<P, 1, WIN><<<hgrid, 256, 0, st>>>(a));
+  DPZ_TIMED(DPZ_KT_EXACT_RESOLVE, st, select_resolve_kernel<P, 1, WIN><<<m, 1024, 0, st>>>(a));
+  DPZ_TIMED(DPZ_KT_EXACT_HIST, st, select_hist_kernel<P, 2, WIN><<<hgrid, 256, 0, st>>>(a));
+  DPZ_TIMED(DPZ_KT_EXACT_RESOLVE, st, select_resolve_kernel<P, 2, WIN><<<m, 1024, 0, st>>>(a));
+  DPZ_TIMED(DPZ_KT_EXACT_COUNT, st, select_count_kernel<P, WIN><<<cgrid, 256, 0, st>>>(a));
+  DPZ_TIMED(DPZ_KT_EXACT_SCAN, st, select_scan_kernel<P, WIN><<<m, 1024, 0, st>>>(a));
+  DPZ_TIMED(DPZ_KT_EXACT_WRITE, st, select_write_kernel<P, WIN><<<cgrid, 256, 0, st>>>(a));
   return DPZ_OK;
 }
 

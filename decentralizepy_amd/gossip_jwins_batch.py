@@ -80,7 +80,15 @@ class JwinsBatchRound(WireCoded, ShardedRound):
 
     def __init__(self, adj, x_init, alpha_list="[0.1, 0.2, 0.3, 0.4, 1.0]", rank=0, world=1,
                  group=None, wavelet="sym2", level=4, metadata_cap=0.5, device=None, ops=None,
-                 float_precision=0, **unknown):
+                 float_precision=0, selection="exact", **unknown):
+        """``selection``: "exact", the nine-launch radix selection, or "window", the one-read
+        selection around the last threshold of the node's alpha (``dpz_jwins_encode_nodes_window``,
+        one prior per node and entry of ``alpha_list``): the same round bit for bit
+        (``selection_status()`` tells which way a node went).  ``ops`` selects exactly either
+        way."""
+        if selection not in ("exact", "window"):
+            raise ValueError(f"selection {selection!r}: 'exact' or 'window'")
+        self.selection = selection
         if unknown:
             raise ValueError(
                 f"unknown arguments {sorted(unknown)}: JwinsBatchRound offers neither compressed "
@@ -126,6 +134,13 @@ class JwinsBatchRound(WireCoded, ShardedRound):
         self.weights = [mh_weights(adj, i) for i in range(self.lo, self.hi)]
         self.alphas = None
         self._lay = self._s_idx = self._s_val = None
+        self._kmax, self._sel_ws = kmax, None
+        self._exact_status = torch.zeros(m, dtype=torch.int32, device=self.device)
+        if self._hip and m and selection == "window" and kmax:
+            from . import codec
+            if len(self.alpha_list) > codec._lib.lib().dpz_jwins_window_slots():
+                raise ValueError(f"selection='window' keeps one prior per entry of alpha_list: "
+                                 f"at most {codec._lib.lib().dpz_jwins_window_slots()} entries")
         if self._hip and m:
             from . import codec
             dev = self.device
@@ -229,13 +244,21 @@ class JwinsBatchRound(WireCoded, ShardedRound):
             for j in range(m):
                 partial, k, oi, ov = self._lay[self.lo + j]
                 pv = base + 4 * (self._s_idx + ov)
-                if partial:
+                if partial and self.selection == "window":
+                    # the prior slot: the drawn alpha's place in alpha_list
+                    self._enc.set(j, k, base + 4 * oi, pv,
+                                  self.alpha_list.index(self.alphas[self.lo + j]))
+                elif partial:
                     self._enc.set(j, k, base + 4 * oi, pv)
                 else:  # Wavelet.py:185-192: all of W(x); copied only where it is gathered
                     self._enc.set(j, 0, 0, pv if self.coll else 0)
             self._enc.upload()
             self._transform_pair(codec)
-            codec.jwins_encode_nodes(self._enc, M, self._ws)
+            if self.selection == "window" and self._kmax:
+                self._sel_ws = codec.jwins_encode_nodes_window(self._enc, M, self._kmax,
+                                                               self._sel_ws)
+            else:
+                codec.jwins_encode_nodes(self._enc, M, self._ws)
             return
         vals = self.send[self._s_idx:self._s_idx + self._s_val].view(torch.float32)
         for j in range(m):
@@ -248,6 +271,15 @@ class JwinsBatchRound(WireCoded, ShardedRound):
                 self.acc[j].zero_()
                 if self.coll:
                     vals[ov:ov + M].copy_(self.wx[j])
+
+    def selection_status(self):
+        """The last encode's status per owned node, an int32 tensor on the engine's device: 0 =
+        exact (no prior for the drawn alpha yet, or a full share), 1 = window hit, 2 = window
+        miss, then exact.  Reading it is the caller's synchronisation."""
+        if self._sel_ws is None:
+            return self._exact_status
+        from . import codec
+        return codec.window_status(self._sel_ws, self.m)
 
     def exchange(self):
         """ONE all-gather of this rank's ``[idx block | val block]``."""

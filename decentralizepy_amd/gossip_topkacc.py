@@ -50,11 +50,18 @@ class TopKAccRound(WireCoded, PackedRowRound):
 
     def __init__(self, adj, x_init, alpha, accumulate_averaging_changes=False, metadata_cap=1.0,
                  rank=0, world=1, group=None, device=None, encode=None, fold=None, post=None,
-                 float_precision=0, coded_exchange=False, **unknown):
+                 float_precision=0, coded_exchange=False, selection="exact", **unknown):
         """adj: adjacency sets of all nodes; x_init: (hi - lo, N) fp32, this rank's nodes' models.
         ``encode(x, x0, acc, counter, k, avg) -> (idx, vals)`` (one node, in place on acc and
         counter), ``fold(local, payloads, weights, w_self, out)`` (``GossipRound``'s) and
-        ``post(acc, x_new, x_old)`` (in place on acc) are injectable (CPU tests)."""
+        ``post(acc, x_new, x_old)`` (in place on acc) are injectable (CPU tests).
+        ``selection``: "exact", the nine-launch radix selection, or "window", the one-read
+        selection around every node's last threshold (``dpz_topkacc_encode_nodes_window``): the
+        same round bit for bit, faster where the thresholds drift by less than 1/16 a round
+        (``selection_status()`` tells).  The injected encode is exact either way."""
+        if selection not in ("exact", "window"):
+            raise ValueError(f"selection {selection!r}: 'exact' or 'window'")
+        self.selection = selection
         if unknown:
             raise ValueError(
                 f"unknown arguments {sorted(unknown)}: TopKAccRound offers neither the peer nor the "
@@ -93,7 +100,8 @@ class TopKAccRound(WireCoded, PackedRowRound):
             self._init_coded(self.k, N, HEADER, HEADER + self.cap)
         self.weights = [mh_weights(adj, i) for i in range(self.lo, self.hi)]
         self._tabs = {}
-        self._fold_tab = self._ws = self._dws = None
+        self._fold_tab = self._ws = self._dws = self._sel_ws = None
+        self._exact_status = torch.zeros(m, dtype=torch.int32, device=self.device)
 
     # ---- views of the packed rows ---------------------------------------------------------------
     def _pay(self, row):
@@ -175,14 +183,27 @@ class TopKAccRound(WireCoded, PackedRowRound):
             from . import codec
             if self.m:
                 mode = codec.DPZ_ACC_ADD if self.avg else codec.DPZ_ACC_ACCUMULATE
-                self._ws = codec.topkacc_encode_nodes(self._tables()["node"], self.N, self.k,
-                                                      mode, self._ws)
+                if self.selection == "window":
+                    self._sel_ws = codec.topkacc_encode_nodes_window(
+                        self._tables()["node"], self.N, self.k, mode, self._sel_ws)
+                else:
+                    self._ws = codec.topkacc_encode_nodes(self._tables()["node"], self.N, self.k,
+                                                          mode, self._ws)
             if self._coded:
                 self._coded_encode()
             return
         for j in range(self.m):
             self._write_row(self.send[j], *self._encode(self.x[j], self.x0[j], self.acc[j],
                                                         self.counter[j], self.k, self.avg))
+
+    def selection_status(self):
+        """The last encode's status per owned node, an int32 tensor on the engine's device: 0 =
+        exact, 1 = window hit, 2 = window miss, then exact.  Reading it is the caller's
+        synchronisation."""
+        if self._sel_ws is None:
+            return self._exact_status
+        from . import codec
+        return codec.window_status(self._sel_ws, self.m)
 
     def fold(self):
         """Every owned node's Metro-Hastings fold into ``out`` (and, on the device, over ``x``)."""

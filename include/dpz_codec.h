@@ -1075,6 +1075,20 @@ size_t dpz_topkacc_encode_workspace_bytes(int m, int64_t n);
 int dpz_topkacc_encode_nodes(int m, const void* node_table, int64_t n, int64_t k, int mode,
                              void* ws, size_t ws_bytes, dpz_stream_t stream);
 int dpz_topkacc_post_nodes(int m, const void* node_table, int64_t n, dpz_stream_t stream);
+/* dpz_topkacc_encode_nodes_window: dpz_topkacc_encode_nodes with the windowed one-read selection
+ * (csrc/dpz_select_window_nodes.h): the same rows, acc and counter bit for bit.  ws is the caller's
+ * ACROSS calls: dpz_topkacc_encode_window_workspace_bytes(m, n, k) DEVICE bytes, 256-byte aligned,
+ * all zero before the first call; it holds every node's prior threshold and candidate lists
+ * (2 n bytes per node up to k = n / 16, (2.5 k / n + 0.1) 4 n above).  A node whose prior
+ * window [T (1 - 1/16), T (1 + 1/16)] brackets this call's k-th key is selected from one stream
+ * over x, x0 and acc; every other node (no prior, another k, a miss, a candidate list over its
+ * capacity) runs the exact launch set, on the device.  Three launches, then the exact set's nine;
+ * nothing is read back.  The first m int32 words of ws hold the nodes' status after the call:
+ * 0 = exact, 1 = window hit, 2 = miss, then exact.  Checks as dpz_topkacc_encode_nodes, before
+ * anything is enqueued; a short workspace is DPZ_ERR_WORKSPACE.                                 */
+size_t dpz_topkacc_encode_window_workspace_bytes(int m, int64_t n, int64_t k);
+int dpz_topkacc_encode_nodes_window(int m, const void* node_table, int64_t n, int64_t k, int mode,
+                                    void* ws, size_t ws_bytes, dpz_stream_t stream);
 
 /* ---- A JWINS round of a rank's nodes at once (decentralizepy_amd/gossip_jwins_batch.py) ----------
  * dpz_dwt_sym2_nodes: dpz_dwt_sym2 of m nodes of one length n and one level (1-4) in ONE launch,
@@ -1118,6 +1132,15 @@ int64_t dpz_jwins_chunk_elems(void);
 size_t dpz_jwins_encode_workspace_bytes(int m, int64_t n);
 int dpz_jwins_encode_nodes(int m, const void* node_table, int64_t n, void* ws, size_t ws_bytes,
                            dpz_stream_t stream);
+/* dpz_jwins_encode_nodes_window: dpz_jwins_encode_nodes with the windowed one-read selection, as
+ * dpz_topkacc_encode_nodes_window.  Word 7 of a node's entry is the prior slot of its k, below
+ * dpz_jwins_window_slots(): one prior per node and slot, a full share (k == 0) reports status 0
+ * and leaves the priors alone.  kmax in [1, n], the largest k of any call on this workspace, sizes
+ * the candidate lists (a k above it is the caller's error, checked by the Python wrapper).      */
+int dpz_jwins_window_slots(void);
+size_t dpz_jwins_encode_window_workspace_bytes(int m, int64_t n, int64_t kmax);
+int dpz_jwins_encode_nodes_window(int m, const void* node_table, int64_t n, int64_t kmax, void* ws,
+                                  size_t ws_bytes, dpz_stream_t stream);
 
 /* ---- The batched JWINS round's transforms for every wavelet (csrc/dpz_wvgen_nodes.hip) -----------
  * dpz_dwt_generic_nodes / dpz_idwt_generic_nodes: dpz_dwt_generic / dpz_idwt_generic (no rewind
