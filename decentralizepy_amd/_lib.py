@@ -309,6 +309,11 @@ SIGNATURES = {
     "dpz_wire_decode_nodes_workspace_bytes": (_size, [_int, _i64, _i64]),
     "dpz_wire_decode_nodes": (_int, [_int, _c_void_p, _c_void_p, _int, _c_void_p, _c_void_p,
                                      _size, _c_void_p]),
+    "dpz_squant_row_words": (_i64, [_i64, _i64]),
+    "dpz_squant_encode_nodes_workspace_bytes": (_size, [_int, _i64]),
+    "dpz_squant_encode_nodes": (_int, [_int, _c_void_p, _c_void_p, _i64, _c_void_p, _size,
+                                       _c_void_p]),
+    "dpz_squant_decode_nodes": (_int, [_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
 }
 
 _lib = None

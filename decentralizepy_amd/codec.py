@@ -2334,6 +2334,69 @@ def quant_encode_nodes(table, n, k, slot_bits, workspace=None):
     return workspace
 
 
+def squant_row_words(count, k):
+    """int32 words of a sparse share's quantised row ``[8 info words | body]`` for ``count`` values
+    at float_precision k: the body holds fields of ``k.bit_length() + 1`` bits."""
+    words = int(_lib.lib().dpz_squant_row_words(int(count), int(k)))
+    if not words:
+        raise ValueError("count and float_precision must lie in [1, 2^30]")
+    return words
+
+
+class SquantTable(JwinsEncodeTable):
+    """The node table of ``squant_encode_nodes`` {val, count, out row, slot_words} and of
+    ``squant_decode_nodes`` {coded row, count, out, slot_words}: 4 64-bit words per node.
+    ``set(j, src, count, dst, slot_words)`` fills node j's words on the host (tensors or
+    addresses); ``upload()`` enqueues the copy to the DEVICE words without waiting for it."""
+
+    def __init__(self, m, device):
+        self.m = m
+        self.host = np.zeros((max(1, m), 4), dtype=np.uint64)
+        self.dev = torch.zeros(max(1, m), 4, dtype=torch.int64, device=device)
+
+    def set(self, j, src, count, dst, slot_words):
+        self.host[j] = (self._addr(src), int(count), self._addr(dst), int(slot_words))
+
+
+def squant_encode_nodes(table, k, workspace=None, check_rc=True):
+    """``quant_encode`` of every value list of ``table`` (an uploaded ``SquantTable``), each with
+    its own count, with float_precision k in two launches whatever the node count: per node the 8
+    info words and the body, bit for bit the single call's, into its row; the info record's status
+    is 1 all zero, 2 non-finite, 3 underflow, 4 a width that does not fit the slot, and the body of
+    such a row is not written.  Nothing is read back.  ``workspace``: a uint8 device tensor kept by
+    the caller (allocated here when None).  Returns ``(workspace, rc)``."""
+    _require(table.dev, torch.int64, "table")
+    m, dev = table.m, table.dev.device
+    need = int(_lib.lib().dpz_squant_encode_nodes_workspace_bytes(
+        m, int(table.host[:m, 1].max()) if m else 0))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    rc = _lib.lib().dpz_squant_encode_nodes(
+        m, _ptr(table.dev), ctypes.c_void_p(table.host.ctypes.data), int(k), _ptr(workspace),
+        workspace.numel(), _stream(dev))
+    if check_rc:
+        check(rc, "dpz_squant_encode_nodes")
+    return workspace, rc
+
+
+def squant_decode_nodes(table, status, check_rc=True):
+    """Every coded row of ``table`` (an uploaded ``SquantTable``) decoded in one launch, w and
+    scale read from the row's info words on the device: ``float32(float64(u - 2^(w-1) + 1) *
+    scale)`` into the node's ``out``.  ``status`` (device int32, m) gets 0, the info record's
+    status, 5 (w outside [2, 32]) or 6 (the count's bits pass the slot); a node with a nonzero
+    status writes nothing.  Returns the library's code (raises unless DPZ_OK when ``check_rc``)."""
+    _require(table.dev, torch.int64, "table")
+    _require(status, torch.int32, "status")
+    m, dev = table.m, table.dev.device
+    if status.numel() < m:
+        raise ValueError(f"status holds {status.numel()} words, {m} nodes need {m}")
+    rc = _lib.lib().dpz_squant_decode_nodes(
+        m, _ptr(table.dev), ctypes.c_void_p(table.host.ctypes.data), _ptr(status), _stream(dev))
+    if check_rc:
+        check(rc, "dpz_squant_decode_nodes")
+    return rc
+
+
 def qdense_tile_elems(n_src):
     """The column tile of the staged quantised fold for ``n_src`` packed rows (0: direct only)."""
     return int(_lib.lib().dpz_qdense_tile_elems(int(n_src)))

@@ -65,11 +65,11 @@ struct StatsLds {
   uint32_t wmax[Q_THREADS / 64];
 };
 
-// The block of 8192-element chunk `chunk`: its pairwise sum goes to sums[chunk], its max|x| bits
-// into one of the max words by an atomic max (order-free).  Nothing waits on another block.
-__device__ __forceinline__ void quant_stats_block(const float* __restrict__ x, int64_t n, int vec,
-                                                  uint32_t* maxw, float* sums, unsigned chunk_id,
-                                                  StatsLds& s) {
+// The statistics of 8192-element chunk `chunk_id`: thread 0 returns its pairwise sum in `chunk`
+// and the bits of its max|x| in `bm` (the other threads' values are unspecified).
+__device__ __forceinline__ void quant_stats_chunk(const float* __restrict__ x, int64_t n, int vec,
+                                                  unsigned chunk_id, StatsLds& s, float& chunk_out,
+                                                  uint32_t& bm_out) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int g = tid >> 3, j = tid & 7;
   const int64_t base = (int64_t)chunk_id * Q_CHUNK;
@@ -189,6 +189,20 @@ __device__ __forceinline__ void quant_stats_block(const float* __restrict__ x, i
   if (tid == 0) {
     uint32_t bm = s.wmax[0];
     for (int w = 1; w < Q_THREADS / 64; ++w) bm = s.wmax[w] > bm ? s.wmax[w] : bm;
+    bm_out = bm;
+    chunk_out = chunk;
+  }
+}
+
+// The block of 8192-element chunk `chunk`: its pairwise sum goes to sums[chunk], its max|x| bits
+// into one of the max words by an atomic max (order-free).  Nothing waits on another block.
+__device__ __forceinline__ void quant_stats_block(const float* __restrict__ x, int64_t n, int vec,
+                                                  uint32_t* maxw, float* sums, unsigned chunk_id,
+                                                  StatsLds& s) {
+  float chunk = 0.0f;
+  uint32_t bm = 0;
+  quant_stats_chunk(x, n, vec, chunk_id, s, chunk, bm);
+  if (threadIdx.x == 0) {
     __hip_atomic_fetch_max(&maxw[chunk_id % Q_SLOTS], bm, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
     sums[chunk_id] = chunk;
@@ -295,6 +309,63 @@ __device__ __forceinline__ void pack_block(const float* __restrict__ x, int64_t 
 
 constexpr int Q_PACK_LDS = Q_SPAN + Q_SPAN / 32;  // dwords of LDS of a pack block
 
+// The info block of one vector: S = P(c0), then S = fl(S + P(cj)) in chunk order, a sequential
+// fp32 chain in one thread over sums staged in LDS (Q_TILE floats at `lds`); then the info record
+// with scale = fl(fl(S / fl(n)) / fl(k)).  Every thread of the block calls it.
+__device__ __forceinline__ void quant_info_block(const QuantParams& q, int64_t n, int k,
+                                                 const float* sums, int32_t* __restrict__ info,
+                                                 uint32_t* lds) {
+  float* tile = reinterpret_cast<float*>(lds);
+  const int64_t nchunks = (n + Q_CHUNK - 1) / Q_CHUNK;
+  // Q_TILE sums per step, zero padded: S + 0 is S, and 0 + c0 is c0, so the chain can start
+  // from 0 and run over whole groups of 16.  The next step's sums are in flight, and the next
+  // group's LDS reads issued, while one thread adds.
+  float S = 0.0f;
+  const int t0 = threadIdx.x, t1 = threadIdx.x + Q_THREADS;
+  float r0 = t0 < nchunks ? sums[t0] : 0.0f;
+  float r1 = t1 < nchunks ? sums[t1] : 0.0f;
+  const float4* t4 = reinterpret_cast<const float4*>(tile);
+  for (int64_t b0 = 0; b0 < nchunks; b0 += Q_TILE) {
+    const int cnt = (int)((nchunks - b0) < Q_TILE ? (nchunks - b0) : Q_TILE);
+    tile[t0] = r0;
+    tile[t1] = r1;
+    __syncthreads();
+    const int64_t nb = b0 + Q_TILE;
+    r0 = nb + t0 < nchunks ? sums[nb + t0] : 0.0f;
+    r1 = nb + t1 < nchunks ? sums[nb + t1] : 0.0f;
+    if (threadIdx.x == 0) {
+      const int groups = (cnt + 15) / 16;
+      float4 cur[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) cur[c] = t4[c];
+      for (int gq = 0; gq < groups; ++gq) {
+        float4 nxt[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) nxt[c] = t4[(4 * (gq + 1) + c) & (Q_TILE / 4 - 1)];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          S = S + cur[c].x;
+          S = S + cur[c].y;
+          S = S + cur[c].z;
+          S = S + cur[c].w;
+          cur[c] = nxt[c];
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    info[QI_STATUS] = q.status;
+    info[QI_W] = q.w;
+    info[QI_PAD] = q.pad;
+    info[QI_SCALE] = (int32_t)__float_as_uint((S / (float)n) / (float)k);
+    info[QI_NORM] = (int32_t)__float_as_uint(q.norm);
+    info[QI_MAX] = (int32_t)__float_as_uint(q.m);
+    info[QI_SUM] = (int32_t)__float_as_uint(S);
+    info[QI_OFF] = (int32_t)q.off;
+  }
+}
+
 // Block `bx` of the pack grid of one vector (1 + ceil(n / Q_SPAN) blocks): every block reduces
 // the statistics pass's 256 max words; block 0 chains the chunk sums and writes the info record,
 // block bx > 0 packs span bx - 1.  Returns the parameters (the same in every block).
@@ -320,58 +391,8 @@ __device__ __forceinline__ QuantParams quant_pack_body(const float* __restrict__
   __syncthreads();
   const QuantParams q = quant_params(mb, n, k, cap_dwords);
   if (bx == 0) {
-    // the extra block, dispatched first: S = P(c0), then S = fl(S + P(cj)) in chunk order, a
-    // sequential fp32 chain in one thread over sums staged in LDS, while the other blocks pack;
-    // then the info record with scale = fl(fl(S / fl(n)) / fl(k))
-    float* tile = reinterpret_cast<float*>(lds);
-    const int64_t nchunks = (n + Q_CHUNK - 1) / Q_CHUNK;
-    // Q_TILE sums per step, zero padded: S + 0 is S, and 0 + c0 is c0, so the chain can start
-    // from 0 and run over whole groups of 16.  The next step's sums are in flight, and the next
-    // group's LDS reads issued, while one thread adds.
-    float S = 0.0f;
-    const int t0 = threadIdx.x, t1 = threadIdx.x + Q_THREADS;
-    float r0 = t0 < nchunks ? sums[t0] : 0.0f;
-    float r1 = t1 < nchunks ? sums[t1] : 0.0f;
-    const float4* t4 = reinterpret_cast<const float4*>(tile);
-    for (int64_t b0 = 0; b0 < nchunks; b0 += Q_TILE) {
-      const int cnt = (int)((nchunks - b0) < Q_TILE ? (nchunks - b0) : Q_TILE);
-      tile[t0] = r0;
-      tile[t1] = r1;
-      __syncthreads();
-      const int64_t nb = b0 + Q_TILE;
-      r0 = nb + t0 < nchunks ? sums[nb + t0] : 0.0f;
-      r1 = nb + t1 < nchunks ? sums[nb + t1] : 0.0f;
-      if (threadIdx.x == 0) {
-        const int groups = (cnt + 15) / 16;
-        float4 cur[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) cur[c] = t4[c];
-        for (int gq = 0; gq < groups; ++gq) {
-          float4 nxt[4];
-#pragma unroll
-          for (int c = 0; c < 4; ++c) nxt[c] = t4[(4 * (gq + 1) + c) & (Q_TILE / 4 - 1)];
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            S = S + cur[c].x;
-            S = S + cur[c].y;
-            S = S + cur[c].z;
-            S = S + cur[c].w;
-            cur[c] = nxt[c];
-          }
-        }
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-      info[QI_STATUS] = q.status;
-      info[QI_W] = q.w;
-      info[QI_PAD] = q.pad;
-      info[QI_SCALE] = (int32_t)__float_as_uint((S / (float)n) / (float)k);
-      info[QI_NORM] = (int32_t)__float_as_uint(q.norm);
-      info[QI_MAX] = (int32_t)__float_as_uint(q.m);
-      info[QI_SUM] = (int32_t)__float_as_uint(S);
-      info[QI_OFF] = (int32_t)q.off;
-    }
+    // the extra block, dispatched first, chains the sums while the other blocks pack
+    quant_info_block(q, n, k, sums, info, lds);
     return q;
   }
   if (q.status != 0) return q;

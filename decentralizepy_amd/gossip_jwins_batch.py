@@ -35,6 +35,15 @@ and sym2 at levels 5-8 with the same legs on ``dpz_dwt_generic_nodes`` /
 ``dpz_idwt_generic_nodes`` (``level`` launches per transform instead of one).  Ties at the k-th
 key go to the lowest indices; finite models only.
 
+With ``compression="EliasQuantization"`` (the reference's ``Wavelet`` / ``JWINS`` with
+``compression_class = EliasQuantization``; ``float_precision`` is the quantiser's k) the values of
+every share, the full ones included (``Wavelet.serialized_model`` -> ``compress_data``), travel
+quantised: after the selection ONE ``dpz_squant_encode_nodes`` call over the owned nodes' value
+lists, each with its own count (k_j, or M for a full share), the all-gather of ``[idx block |
+quantised rows]``, and ONE ``dpz_squant_decode_nodes`` call of every gathered row this rank folds
+into an fp32 value block, which the unchanged fold reads behind the decode's status words.  The
+sender's own W(x) stays unquantised.
+
 ``wire_bytes()`` / ``wire_payload(q)`` (``gossip_round.WireCoded``) give what the round's payloads
 are on the wire with ``compression_class = EliasFpzip`` at ``float_precision``; ``step()`` does not
 call them.
@@ -50,7 +59,7 @@ import torch
 
 from .gossip import mh_weights
 from .gossip_jwins import ALIGN, JwinsRound, _al
-from .gossip_round import ShardedRound, WireCoded
+from .gossip_round import ShardedRound, WireCoded, shard, up4
 
 LEGS = ("encode", "exchange", "fold", "post")
 
@@ -80,8 +89,10 @@ class JwinsBatchRound(WireCoded, ShardedRound):
 
     def __init__(self, adj, x_init, alpha_list="[0.1, 0.2, 0.3, 0.4, 1.0]", rank=0, world=1,
                  group=None, wavelet="sym2", level=4, metadata_cap=0.5, device=None, ops=None,
-                 float_precision=0, selection="exact", **unknown):
-        """``selection``: "exact", the nine-launch radix selection, or "window", the one-read
+                 float_precision=0, selection="exact", compression=None, **unknown):
+        """``compression``: None, or "EliasQuantization": every share's values are exchanged
+        through the reference's quantiser with k = ``float_precision``, an int in [1, 2^30] (HIP
+        only).  ``selection``: "exact", the nine-launch radix selection, or "window", the one-read
         selection around the last threshold of the node's alpha (``dpz_jwins_encode_nodes_window``,
         one prior per node and entry of ``alpha_list``): the same round bit for bit
         (``selection_status()`` tells which way a node went).  ``ops`` selects exactly either
@@ -105,7 +116,7 @@ class JwinsBatchRound(WireCoded, ShardedRound):
                                  "coefficients: an empty payload is not a share")
         self._hip = ops is None
         self.ops = ops
-        self._init_wire(float_precision, [round(a * M) for a in partial])
+        self._init_wire(float_precision, [round(a * M) for a in partial], compression=compression)
         # JWINS.__init__: random.seed(uid) in every node process; every rank replays every node's
         # draws, so every payload's size and place are known everywhere
         self.rngs = [random.Random(uid) for uid in range(self.n_nodes)]
@@ -129,6 +140,16 @@ class JwinsBatchRound(WireCoded, ShardedRound):
         self._cap = self.per * (_al(kmax) + _al(max(kmax, M if full else 0)))
         self._cap = max(self._cap, 2 * ALIGN)
         i32 = dict(dtype=torch.int32, device=self.device)
+        if self._squant:
+            # on the wire [idx block | quantised rows]; the selection's values stay in ``_vraw``
+            # (a node's at its idx offset), the receivers' decoded values go to ``_dvals``
+            self._sq_cache = {}
+            vcap = _al(max(kmax, M if full else 0))
+            qcap = max(self._sq_words(kmax) if kmax else 0, self._sq_words(M) if full else 0)
+            self._cap = max(ALIGN, self.per * _al(kmax)) + max(ALIGN, self.per * qcap)
+            f32 = dict(dtype=torch.float32, device=self.device)
+            self._vraw = torch.zeros(max(ALIGN, self.per * _al(kmax)), **f32)
+            self._dvals = torch.zeros(max(ALIGN, world * self.per * vcap), **f32)
         self.send = torch.zeros(self._cap, **i32)
         self.recv = torch.zeros(world * self._cap, **i32) if self.coll else None
         self.weights = [mh_weights(adj, i) for i in range(self.lo, self.hi)]
@@ -150,6 +171,12 @@ class JwinsBatchRound(WireCoded, ShardedRound):
                 max(256, int(codec._lib.lib().dpz_jwins_encode_workspace_bytes(m, M))),
                 dtype=torch.uint8, device=dev)
             self._guard = torch.zeros(1, **i32)
+            if self._squant:
+                self._sq_enc = codec.SquantTable(m, dev)
+                self._sq_nodes = sorted({q for i in range(self.lo, self.hi) for q in adj[i]})
+                self._sq_dec = codec.SquantTable(len(self._sq_nodes), dev)
+                # the decode's status words are the fold's guard
+                self._guard = self.guard = torch.zeros(max(1, len(self._sq_nodes)), **i32)
             maxp = max((len(nb) for nb, _, _ in self.weights), default=1)
             self._dws = codec.Workspace(dev).get_decode(M, max(1, maxp))
             counts, w, ws_ = [], [], []
@@ -199,16 +226,65 @@ class JwinsBatchRound(WireCoded, ShardedRound):
     # ---- layout of one round's payloads ------------------------------------------------------
     def _place(self, q):
         """Node q's (partial, k, word offset of its idx slot, of its val slot) in the buffer the
-        folds read (every rank's blocks after an all-gather, this rank's in place)."""
+        folds read (every rank's blocks after an all-gather, this rank's in place).  With
+        ``compression`` the val offset is into ``_dvals``, the decoded values."""
         partial, k, oi, ov = self._lay[q]
-        base = (q // self.per) * (self._s_idx + self._s_val) if self.coll else 0
+        r = q // self.per if self.coll else 0
+        if self._squant:
+            return partial, k, r * (self._s_idx + self._s_q) + oi, r * self._s_val + ov
+        base = r * (self._s_idx + self._s_val)
         return partial, k, base + oi, base + self._s_idx + ov
+
+    # ---- the EliasQuantization exchange (gossip_round.WireCoded) ------------------------------
+    def _sq_words(self, count):
+        """int32 words of the quantised row of ``count`` values, rows 16-byte aligned."""
+        w = self._sq_cache.get(count)
+        if w is None:
+            from . import codec
+            w = self._sq_cache[count] = up4(codec.squant_row_words(count, self.float_precision))
+        return w
+
+    def _sq_layout(self):
+        """Per node the word offset of its quantised row inside its rank's block of rows, and
+        the padded block size (identical on every rank)."""
+        oq, s_q = [0] * self.n_nodes, 0
+        for r in range(self.world):
+            lo, hi, _ = shard(self.n_nodes, self.world, r)
+            o = 0
+            for q in range(lo, hi):
+                oq[q] = o
+                o += self._sq_words(self._lay[q][1] or self.M)
+            s_q = max(s_q, o)
+        return oq, max(ALIGN, s_q)
+
+    def _squant_rows(self):
+        rows = []
+        for q in range(self.lo, self.hi):
+            count = self._lay[q][1] or self.M
+            o = self._s_idx + self._oq[q]
+            rows.append((count, self.send[o:o + self._sq_words(count)]))
+        return rows
+
+    def _squant_exchange_decode(self):
+        """ONE decode of every gathered row this rank folds into its place in ``_dvals``."""
+        buf = self.recv if self.coll else self.send
+        W = self._s_idx + self._s_q
+        for j, q in enumerate(self._sq_nodes):
+            _, k, _, pv = self._place(q)
+            count = k or self.M
+            r = q // self.per if self.coll else 0
+            self._sq_dec.set(j, buf.data_ptr() + 4 * (r * W + self._s_idx + self._oq[q]), count,
+                             self._dvals.data_ptr() + 4 * pv, self._sq_words(count))
+        self._sq_dec.upload()
+        self._squant_decode(self._sq_dec, self.guard)
 
     def payload(self, q):
         """``(idx or None, vals)`` of node q's payload of the last round (an owned node; any
         node after an all-gather).  A full share has no indices."""
         partial, k, pi, pv = self._place(q)
         buf = self.recv if self.coll else self.send
+        if self._squant:  # what the receivers decoded
+            return buf[pi:pi + k] if partial else None, self._dvals[pv:pv + (k or self.M)]
         if partial:
             return buf[pi:pi + k], buf[pv:pv + k].view(torch.float32)
         if not self.coll:
@@ -221,6 +297,8 @@ class JwinsBatchRound(WireCoded, ShardedRound):
         views = []
         for j in range(self.m):
             partial, k, oi, ov = self._lay[self.lo + j]
+            if self._squant:  # the selection's own values, at the index offsets
+                vals, ov = self._vraw, oi
             views.append((self.send[oi:oi + k], vals[ov:ov + k]) if partial
                          else (None, self.wx[j]))
         return self.M, views
@@ -244,6 +322,12 @@ class JwinsBatchRound(WireCoded, ShardedRound):
             for j in range(m):
                 partial, k, oi, ov = self._lay[self.lo + j]
                 pv = base + 4 * (self._s_idx + ov)
+                if self._squant:
+                    # the values stay here: the quantiser reads them (a full share's from wx)
+                    pv = self._vraw.data_ptr() + 4 * oi if partial else 0
+                    o = self._s_idx + self._oq[self.lo + j]
+                    self._sq_enc.set(j, pv or self.wx[j], k or M, base + 4 * o,
+                                     self._sq_words(k or M))
                 if partial and self.selection == "window":
                     # the prior slot: the drawn alpha's place in alpha_list
                     self._enc.set(j, k, base + 4 * oi, pv,
@@ -253,12 +337,16 @@ class JwinsBatchRound(WireCoded, ShardedRound):
                 else:  # Wavelet.py:185-192: all of W(x); copied only where it is gathered
                     self._enc.set(j, 0, 0, pv if self.coll else 0)
             self._enc.upload()
+            if self._squant:
+                self._sq_enc.upload()
             self._transform_pair(codec)
             if self.selection == "window" and self._kmax:
                 self._sel_ws = codec.jwins_encode_nodes_window(self._enc, M, self._kmax,
                                                                self._sel_ws)
             else:
                 codec.jwins_encode_nodes(self._enc, M, self._ws)
+            if self._squant:
+                self._squant_encode(self._sq_enc)
             return
         vals = self.send[self._s_idx:self._s_idx + self._s_val].view(torch.float32)
         for j in range(m):
@@ -284,8 +372,10 @@ class JwinsBatchRound(WireCoded, ShardedRound):
     def exchange(self):
         """ONE all-gather of this rank's ``[idx block | val block]``."""
         if self.coll:
-            W = self._s_idx + self._s_val
+            W = self._s_idx + (self._s_q if self._squant else self._s_val)
             self.all_gather(self.recv[:self.world * W], self.send[:W])
+        if self._squant and self.m:
+            self._squant_exchange_decode()
 
     def fold(self):
         """Every owned node's Metro-Hastings fold over its W(x) into its ``wc`` row."""
@@ -300,6 +390,7 @@ class JwinsBatchRound(WireCoded, ShardedRound):
             return
         from . import _lib
         base = (self.recv if self.coll else self.send).data_ptr()
+        vbase = self._dvals.data_ptr() if self._squant else base
         wx0, wstep = self.wx.data_ptr(), self.wx.stride(0) * 4
         idx, val, kk = [], [], []
         for nbrs, _, _ in self.weights:
@@ -307,11 +398,12 @@ class JwinsBatchRound(WireCoded, ShardedRound):
                 partial, k, pi, pv = self._place(q)
                 if partial:
                     idx.append(base + 4 * pi)
-                    val.append(base + 4 * pv)
+                    val.append(vbase + 4 * pv)
                     kk.append(k)
                 else:
                     idx.append(None)
-                    val.append(base + 4 * pv if self.coll else wx0 + (q - self.lo) * wstep)
+                    val.append(vbase + 4 * pv if self.coll or self._squant
+                               else wx0 + (q - self.lo) * wstep)
                     kk.append(M)
         ft, tot = self._fold_tab, self._tot
         idx_a, val_a = (ctypes.c_void_p * tot)(*idx), (ctypes.c_void_p * tot)(*val)
@@ -320,7 +412,11 @@ class JwinsBatchRound(WireCoded, ShardedRound):
         L = _lib.lib()
         rc = L.dpz_decode_average_batch_guarded(
             m, ft["local"], ft["out"], M, ft["np"], idx_a, val_a, k_a, ft["w"], ft["w_self"],
-            _lib.DPZ_FOLD_SELF, self._guard.data_ptr(), 1, stream)
+            _lib.DPZ_FOLD_SELF, self._guard.data_ptr(), self._guard.numel(), stream)
+        if rc == _lib.DPZ_ERR_UNSUPPORTED and self._squant:
+            raise _lib.CodecError("compression='EliasQuantization' folds behind the decode's "
+                                  "status words: M >= 1024, two owned nodes or more, every node "
+                                  "with a neighbour")
         if rc == _lib.DPZ_ERR_UNSUPPORTED:  # M < 1024 or a node without neighbours: node after node
             rc = L.dpz_decode_average_batch(
                 m, ft["local"], ft["out"], M, ft["np"], idx_a, val_a, k_a, ft["w"], ft["w_self"],
@@ -343,12 +439,18 @@ class JwinsBatchRound(WireCoded, ShardedRound):
                 self.ops.accumulate(self.acc[j], self.x[j], self.x0[j])
         self._x0buf.copy_(self._xbuf)  # every row at once, the rows' padding included
 
+    def draw(self):
+        """Every node's alpha of the coming round and the layout of the round's payloads."""
+        self.alphas = [rng.choice(self.alpha_list) for rng in self.rngs]
+        self._lay, self._s_idx, self._s_val = JwinsRound._layout(self, self.alphas)
+        if self._squant:
+            self._oq, self._s_q = self._sq_layout()
+
     def step(self, mark=None):
         """One round.  Nothing synchronises with the host.  ``mark(leg)`` is called after each of
         ``LEGS`` is enqueued (tools/bench_jwins_round.py records an event)."""
         mark = mark or (lambda leg: None)
-        self.alphas = [rng.choice(self.alpha_list) for rng in self.rngs]
-        self._lay, self._s_idx, self._s_val = JwinsRound._layout(self, self.alphas)
+        self.draw()
         self.encode()
         mark("encode")
         self.exchange()

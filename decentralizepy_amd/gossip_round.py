@@ -3,8 +3,11 @@ gossip_subsampling.py, gossip_epidemic.py, gossip_choco.py, gossip_quant.py, gos
 gossip_topkacc.py, gossip_fft.py) share:
 ``ShardedRound``, the sharding of the nodes over the ranks, ``PackedRowRound``, the packed row
 per node that one all-gather exchanges, and ``WireCoded``, the EliasFpzip wire streams of a round's
-payloads in one batched call and the exchange that carries them."""
+payloads in one batched call and the exchange that carries them, and the EliasQuantization
+exchange (``compression="EliasQuantization"``): the payloads' values through the reference's
+quantiser, one batched call each way."""
 import math
+import pickle
 
 import numpy as np
 import torch
@@ -68,7 +71,27 @@ class WireCoded:
     * ``_wire_message(q, indices, params)``: the dict the plugin puts on the wire for node q
       (``indices`` None for a full share)."""
 
-    def _init_wire(self, float_precision, partial_ks, coded_exchange=False):
+    COMPRESSIONS = (None, "EliasQuantization")
+
+    def _init_wire(self, float_precision, partial_ks, coded_exchange=False, compression=None):
+        if compression not in self.COMPRESSIONS:
+            raise ValueError(f"compression {compression!r}: None or 'EliasQuantization' (the "
+                             "EliasFpzip streams are wire_payload() / coded_exchange)")
+        self._squant = compression is not None
+        if self._squant:
+            # float_precision is the quantiser's k, as Sharing.__init__ hands it to the compressor
+            k = float_precision
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+                raise TypeError(f"float_precision must be an int, got {type(k).__name__}")
+            if not 1 <= int(k) <= 2 ** 30:
+                raise ValueError("float_precision must be in [1, 2^30]")
+            if coded_exchange:
+                raise ValueError("coded_exchange carries the EliasFpzip streams: not with "
+                                 "compression='EliasQuantization'")
+            if not self._hip:
+                raise NotImplementedError("compression='EliasQuantization' quantises with the HIP "
+                                          "codec only; the CPU stand-in has no quantiser")
+        self.compression = compression
         self.float_precision = int(float_precision)
         if self.float_precision < 0:
             raise ValueError("float_precision must be >= 0 (0 or >= 32: lossless)")
@@ -128,8 +151,10 @@ class WireCoded:
         if m:
             self._wire_ws = codec.wire_nodes_workspace(
                 m, max(v.numel() for _, v in views), self.device, self._wire_ws)
-            codec.wire_encode_nodes(self._wire_tab, sizes, status, self.float_precision,
-                                    self._wire_ws)
+            codec.wire_encode_nodes(self._wire_tab, sizes, status,
+                                    0 if self._squant else self.float_precision, self._wire_ws)
+        if self._squant:  # the values travel quantised: the reference's ``to_send``
+            sizes[:m, 1] = self._squant_value_bytes()
         self._wire_sizes = sizes[:m]
         return sizes[:m], status[:m], buf, [(oi if ci else None, ov) for oi, ci, ov, _ in caps]
 
@@ -188,20 +213,117 @@ class WireCoded:
         self.csend[:m, H:H + 4].copy_(self._enc_sizes[:m].view(torch.int32))
         torch.bitwise_or(self.send[:m, 2], self._enc_status[:m], out=self.csend[:m, 2])
 
+    # ---- the EliasQuantization exchange ----------------------------------------------------------
+    # What the engines share: the two tables' calls, and the wire view of a quantised row.  An
+    # engine provides ``_squant_rows()``: per owned node (count, its coded row [8 info words |
+    # body] as an int32 view) of the last encode.
+    def _squant_encode(self, table):
+        """ONE ``squant_encode_nodes`` call over the owned nodes' value lists."""
+        from . import codec
+        if table.m:
+            self._sq_ws, _ = codec.squant_encode_nodes(table, self.float_precision,
+                                                       getattr(self, "_sq_ws", None))
+
+    def _squant_decode(self, table, status):
+        """ONE ``squant_decode_nodes`` call over the gathered rows this rank folds."""
+        from . import codec
+        if table.m:
+            codec.squant_decode_nodes(table, status)
+
+    def _squant_value_bytes(self):
+        """Device int64 (m): 2 + ceil(count w / 8), the length of the reference's ``to_send``."""
+        rows = self._squant_rows()
+        if not rows:
+            return torch.zeros(0, dtype=torch.int64, device=self.device)
+        w = torch.stack([row[1] for _, row in rows]).to(torch.int64)
+        counts = torch.tensor([c for c, _ in rows], dtype=torch.int64).to(self.device)
+        return 2 + (counts * w + 7) // 8
+
+    def _squant_params(self, q):
+        """Owned node q's quantised values as the plugin's wire value: ``pickle((np.float32(scale),
+        uint8[padding, w, body...]))`` (compression/Quantization.py).  Blocks."""
+        count, row = self._squant_rows()[q - self.lo]
+        info = row[:8].cpu().numpy()
+        if info[0]:
+            raise RuntimeError(f"quantised values of node {q} refused (status {int(info[0])})")
+        w, pad = int(info[1]), int(info[2])
+        nbytes = (count * w + 7) // 8
+        body = row[8:8 + (nbytes + 3) // 4].cpu().numpy().view(np.uint8)[:nbytes]
+        to_send = np.concatenate([np.array([pad, w], dtype=np.uint8), body])
+        return pickle.dumps((info[3:4].view(np.float32)[0], to_send))
+
+    # ---- the EliasQuantization exchange of rows of equal k, PackedRowRound's layout -------------
+    def _init_squant_rows(self, k, idx_words, val_word):
+        """After ``_alloc_rows``: a coded row is ``[header | idx_words raw int32 index words | 8
+        info words | body]``, the raw row's first ``HEADER + idx_words`` words followed by the
+        quantised row of its k values at ``val_word``.  ``csend`` holds this rank's, ``crecv``
+        every rank's after the all-gather; the decode writes the values into the raw-layout rows
+        of ``recv``, which the folds read with the indices of ``crecv``."""
+        from . import codec
+        H, i32 = PackedRowRound.HEADER, dict(dtype=torch.int32, device=self.device)
+        self._sq_head = H + idx_words
+        self._sq_slot = slot = up4(codec.squant_row_words(k, self.float_precision))
+        self.csend = torch.zeros(self.per, self._sq_head + slot, **i32)
+        self.crecv = torch.zeros(self.per * self.world, self.csend.shape[1],
+                                 **i32) if self.coll else self.csend
+        if self.recv is None:
+            self.recv = torch.zeros(self.per * self.world, self.row_words, **i32)
+        self._enc_tab = codec.SquantTable(self.m, self.device)
+        for j in range(self.m):
+            self._enc_tab.set(j, self.send[j].data_ptr() + 4 * val_word, k,
+                              self.csend[j].data_ptr() + 4 * self._sq_head, slot)
+        self._enc_tab.upload()
+        nodes = sorted({q for i in range(self.lo, self.hi) for q in self.adj[i]})
+        self._dec_tab = codec.SquantTable(len(nodes), self.device)
+        for j, q in enumerate(nodes):
+            self._dec_tab.set(j, self.crecv[q].data_ptr() + 4 * self._sq_head, k,
+                              self.recv[q].data_ptr() + 4 * val_word, slot)
+        self._dec_tab.upload()
+        self._dec_status = torch.zeros(max(1, len(nodes)), **i32)
+        self._dec_all = nodes == list(range(self.per * self.world))
+        self._dec_nodes = torch.tensor(nodes, dtype=torch.int64, device=self.device)
+        self._sq_k = k
+
+    def _squant_rows(self):
+        return [(self._sq_k, self.csend[j, self._sq_head:]) for j in range(self.m)]
+
+    def _squant_rows_encode(self):
+        """After the selection: the header and index words copied, the values quantised."""
+        m = self.m
+        if m:
+            self.csend[:m, :self._sq_head].copy_(self.send[:m, :self._sq_head])
+            self._squant_encode(self._enc_tab)
+
     @property
     def rows(self):
         """The rows the folds read: the decoded ones with a coded exchange."""
-        return self.recv if self._coded else super().rows
+        return self.recv if self._coded or self._squant else super().rows
+
+    @property
+    def idx_rows(self):
+        """The rows whose index words the folds read: with the EliasQuantization exchange the
+        gathered rows themselves (the indices travel raw)."""
+        return self.crecv if self._squant else self.rows
 
     def exchange(self):
         """With ``coded_exchange``: ONE all-gather of the coded rows (in place with one rank and no
         group), then ONE ``wire_decode_nodes`` call into the raw-layout receive buffer; the decode
         status is ORed into the guard words of the guarded fold."""
-        if not self._coded:
+        if not self._coded and not self._squant:
             return super().exchange()
         from . import codec
         if self.coll:
             self.all_gather(self.crecv, self.csend)
+        if self._squant:
+            # one decode of every gathered row this rank folds; a refused row (the sender's
+            # quantiser status, a bad width, a count past the slot) goes into the guard words
+            self._squant_decode(self._dec_tab, self._dec_status)
+            if self._dec_all:
+                return torch.bitwise_or(self.crecv[:, 2], self._dec_status, out=self.guard)
+            self.guard.copy_(self.crecv[:, 2])
+            if self._dec_tab.m:
+                self.guard[self._dec_nodes] |= self._dec_status
+            return None
         if not self._dec_tab.m:
             return self.guard.copy_(self.crecv[:, 2])
         codec.wire_decode_nodes(self._dec_tab, self._dec_status, self.float_precision,
@@ -229,7 +351,10 @@ class WireCoded:
         ``EliasFpzip`` codes them at this engine's ``float_precision``.  One batched size-only
         call of two launches; nothing synchronises with the host.  The pickle framing that the
         reference's ``TCP.encrypt`` adds is not counted: it is made on the host and is the same
-        for every message of a configuration."""
+        for every message of a configuration.
+        With ``compression="EliasQuantization"`` the second column is ``2 + ceil(count w / 8)``,
+        the length of the uint8 array ``to_send`` of the reference's quantiser at the width w the
+        node's values gave; the pickle framing of ``(scale, to_send)`` is excluded as well."""
         if self._coded:  # the coded rows' header words: nothing is launched
             if not self._wire_encoded:
                 raise RuntimeError("no round has been encoded yet")
@@ -265,6 +390,8 @@ class WireCoded:
                 (None if oi is None else host[oi:oi + nb_i].copy(), host[ov:ov + nb_v].copy())
                 for (oi, ov), (nb_i, nb_v) in zip(offs, sizes.tolist())]
         indices, params = self._wire_streams[q - self.lo]
+        if self._squant:  # compression.EliasQuantization decodes it: Elias indices, pickled values
+            params = self._squant_params(q)
         return self._wire_message(q, indices, params)
 
 

@@ -24,7 +24,12 @@ fold's output.  With ``coded_exchange=True`` the all-gather carries the rows as 
 streams instead (``gossip_round.WireCoded``): one ``dpz_wire_encode_nodes`` call after the
 selection, one ``dpz_wire_decode_nodes`` call after the all-gather, and the fold reads what the
 receivers decoded, so ``float_precision = p`` folds values truncated to their top p bits as the
-reference's ``EliasFpzipLossy`` round does.  In mode "avg" the encode's key vector goes into the fold's output row, which is
+reference's ``EliasFpzipLossy`` round does.  With ``compression="EliasQuantization"`` the all-gather
+carries ``[header | raw indices | the quantised values]`` instead: one ``dpz_squant_encode_nodes``
+call after the selection (``float_precision`` is the quantiser's k), one
+``dpz_squant_decode_nodes`` call after the all-gather, and the fold reads what the receivers
+decoded, the reference's ``PartialModel`` round with ``compression_class = EliasQuantization``
+(the sender's own model stays unquantised).  In mode "avg" the encode's key vector goes into the fold's output row, which is
 free until the fold: no extra allocation.  Nothing synchronises with the host inside ``step()``.
 
 Ties at the k-th key go to the lowest indices (``torch.topk``'s order is implementation-defined).
@@ -50,7 +55,8 @@ class TopKAccRound(WireCoded, PackedRowRound):
 
     def __init__(self, adj, x_init, alpha, accumulate_averaging_changes=False, metadata_cap=1.0,
                  rank=0, world=1, group=None, device=None, encode=None, fold=None, post=None,
-                 float_precision=0, coded_exchange=False, selection="exact", **unknown):
+                 float_precision=0, coded_exchange=False, selection="exact", compression=None,
+                 **unknown):
         """adj: adjacency sets of all nodes; x_init: (hi - lo, N) fp32, this rank's nodes' models.
         ``encode(x, x0, acc, counter, k, avg) -> (idx, vals)`` (one node, in place on acc and
         counter), ``fold(local, payloads, weights, w_self, out)`` (``GossipRound``'s) and
@@ -58,7 +64,9 @@ class TopKAccRound(WireCoded, PackedRowRound):
         ``selection``: "exact", the nine-launch radix selection, or "window", the one-read
         selection around every node's last threshold (``dpz_topkacc_encode_nodes_window``): the
         same round bit for bit, faster where the thresholds drift by less than 1/16 a round
-        (``selection_status()`` tells).  The injected encode is exact either way."""
+        (``selection_status()`` tells).  The injected encode is exact either way.
+        ``compression``: None, or "EliasQuantization": the values are exchanged through the
+        reference's quantiser with k = ``float_precision``, an int in [1, 2^30] (HIP only)."""
         if selection not in ("exact", "window"):
             raise ValueError(f"selection {selection!r}: 'exact' or 'window'")
         self.selection = selection
@@ -82,7 +90,7 @@ class TopKAccRound(WireCoded, PackedRowRound):
                              "use gossip_subsampling.SubSamplingRound for tiny random shares")
         self._hip = not any(injected)
         self._encode, self._fold, self._post = encode, fold, post
-        self._init_wire(float_precision, [self.k], coded_exchange)
+        self._init_wire(float_precision, [self.k], coded_exchange, compression)
         self.cap = up4(self.k)
         stride = up4(N)  # every row 16-byte aligned
         self._state = torch.zeros(4, max(1, m), stride, dtype=torch.float32, device=self.device)
@@ -98,21 +106,24 @@ class TopKAccRound(WireCoded, PackedRowRound):
         self._alloc_rows(HEADER + 2 * self.cap)
         if self._coded:
             self._init_coded(self.k, N, HEADER, HEADER + self.cap)
+        if self._squant:
+            self._init_squant_rows(self.k, self.cap, HEADER + self.cap)
         self.weights = [mh_weights(adj, i) for i in range(self.lo, self.hi)]
         self._tabs = {}
         self._fold_tab = self._ws = self._dws = self._sel_ws = None
         self._exact_status = torch.zeros(m, dtype=torch.int32, device=self.device)
 
     # ---- views of the packed rows ---------------------------------------------------------------
-    def _pay(self, row):
-        return (row[HEADER:HEADER + self.k],
+    def _pay(self, row, idx_row=None):
+        idx_row = row if idx_row is None else idx_row
+        return (idx_row[HEADER:HEADER + self.k],
                 row[HEADER + self.cap:HEADER + self.cap + self.k].view(torch.float32))
 
     def payload(self, q):
         """``(idx, vals)`` of node q's payload of its last encode (an owned node; any node after
-        an all-gather).  With ``coded_exchange``: what the receivers fold, the decoded payload of
-        the last exchange (an owned node's own selection stays in ``send``)."""
-        return self._pay(self._row(q))
+        an all-gather).  With ``coded_exchange`` or ``compression``: what the receivers fold, the
+        decoded payload of the last exchange (an owned node's own selection stays in ``send``)."""
+        return self._pay(self._row(q), self.idx_rows[q])
 
     # ---- the wire layer's hooks (gossip_round.WireCoded) -----------------------------------------
     def _wire_views(self):
@@ -158,12 +169,12 @@ class TopKAccRound(WireCoded, PackedRowRound):
         rows, which do not move between rounds."""
         if self._fold_tab is None:
             counts, idx, val, w, ws_ = [], [], [], [], []
-            step = self.rows.stride(0) * 4
+            step, istep = self.rows.stride(0) * 4, self.idx_rows.stride(0) * 4
             for nbrs, wj, w_self in self.weights:
                 counts.append(len(nbrs))
                 for q in nbrs:
                     row = self.rows.data_ptr() + q * step
-                    idx.append(row + 4 * HEADER)
+                    idx.append(self.idx_rows.data_ptr() + q * istep + 4 * HEADER)
                     val.append(row + 4 * (HEADER + self.cap))
                 w.extend(wj)
                 ws_.append(w_self)
@@ -191,6 +202,8 @@ class TopKAccRound(WireCoded, PackedRowRound):
                                                           mode, self._ws)
             if self._coded:
                 self._coded_encode()
+            if self._squant:
+                self._squant_rows_encode()
             return
         for j in range(self.m):
             self._write_row(self.send[j], *self._encode(self.x[j], self.x0[j], self.acc[j],
@@ -221,6 +234,10 @@ class TopKAccRound(WireCoded, PackedRowRound):
         rc = _lib.lib().dpz_decode_average_batch_guarded(
             self.m, tab["local"], tab["out"], self.N, ft["np"], ft["idx"], ft["val"], ft["k"],
             ft["w"], ft["w_self"], flags, self.guard.data_ptr(), self.guard.numel(), stream)
+        if rc == _lib.DPZ_ERR_UNSUPPORTED and self._squant:
+            raise _lib.CodecError("compression='EliasQuantization' folds behind the decode's "
+                                  "status words: N >= 1024, two owned nodes or more, every node "
+                                  "with a neighbour")
         if rc == _lib.DPZ_ERR_UNSUPPORTED:  # N < 1024 or a node without neighbours: node after node
             if self._dws is None:
                 self._dws = codec.Workspace(self.device)

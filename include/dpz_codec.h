@@ -1321,6 +1321,48 @@ size_t dpz_wire_decode_nodes_workspace_bytes(int m, int64_t max_idx_cap, int64_t
 int dpz_wire_decode_nodes(int m, const void* table, const void* host_table, int precision,
                           uint32_t* status, void* ws, size_t ws_bytes, dpz_stream_t stream);
 
+/* ---- The quantiser over the value lists of a sparse round (csrc/dpz_squant_nodes.hip) ------------
+ * EliasQuantization over PartialModel / Wavelet / JWINS payloads: the values of a sparse share go
+ * through the quantiser above, the indices stay lossless.  Both calls take a DEVICE table of m
+ * entries of 4 64-bit words and its HOST copy, on which every check is made before anything is
+ * enqueued; nothing is zeroed, read back or synchronised.
+ * dpz_squant_encode_nodes: entry {val (fp32, 4-byte aligned), count, out row, slot_words}.  The
+ * out row is [8 info words of dpz_quant_encode | body], slot_words int32 words in all.  Per node
+ * the info words and the body are bit for bit what dpz_quant_encode(val, count, k, body, 4 *
+ * (slot_words - 8), ...) writes, the statuses 1-4 included (4: the width found does not fit the
+ * slot); nothing is written to the body of a node whose status is nonzero and nothing past a slot.
+ * TWO launches whatever m is: statistics, grid (chunks of 8192 of the largest count, nodes), a
+ * block writing its chunk's max|v| and pairwise sum to words of its own (no atomics, the result
+ * does not depend on the grid); pack, grid (1 + spans of 8192, nodes): block 0 of a node chains
+ * its chunk sums and writes the info record, the others stage a span's fields in LDS (16-byte
+ * loads of a 16-byte aligned list, per-element loads otherwise, decided per node on the device)
+ * and assemble whole 32-bit words of the stream, one per lane, from the <= 2 + 32/w fields that
+ * touch it.  Timed as "quant_stats" and "quant_pack".
+ * dpz_squant_row_words(count, k) = 8 + ceil(count * w_max / 32) with w_max = bit_length(k) + 1:
+ * the slot that holds every width k gives while max|v| / k is a normal number (0 for a count or
+ * k outside [1, 2^30]).  ws: dpz_squant_encode_nodes_workspace_bytes(m, largest count) DEVICE
+ * bytes, 8-byte aligned, any content (0 for m < 1 or a count outside [1, 2^30]).
+ * dpz_squant_decode_nodes: entry {coded row, count, out (fp32 values), slot_words}; w and scale
+ * are read from the row's info words on the device; out[i] = float(double(u_i - 2^(w-1) + 1) *
+ * double(scale)), dpz_quant_decode's value.  ONE launch, grid (tiles of 4096 values of the largest
+ * count, nodes): a tile starts on a dword of the body, its dwords are staged in LDS (16-byte
+ * loads of an aligned body), a lane extracts four consecutive MSB-first fields per step and stores
+ * them with one 16-byte store where out is aligned.  Timed as "quant_unpack".
+ *   status[j] (DEVICE uint32, written for every node): 0; the info record's status 1-4 if that is
+ *   nonzero; 5 for a w outside [2, 32]; 6 for count * w bits beyond slot_words - 8 words.  With a
+ *   nonzero status nothing of that node is written and only its 8 info words are read; no read
+ *   leaves a slot; no other node is affected.
+ * Before anything is enqueued, both: DPZ_ERR_ARG for m < 1, a null or misaligned table (8
+ * bytes), a null host table, a null val / row / out or one not 4-byte aligned, a count outside
+ * [1, 2^30], slot_words < 8, and k outside [1, 2^30] / a null or misaligned (4 bytes) status;
+ * DPZ_ERR_UNSUPPORTED for m > 65535; DPZ_ERR_WORKSPACE for a null or short workspace.            */
+int64_t dpz_squant_row_words(int64_t count, int64_t k);
+size_t dpz_squant_encode_nodes_workspace_bytes(int m, int64_t max_count);
+int dpz_squant_encode_nodes(int m, const void* table, const void* host_table, int64_t k, void* ws,
+                            size_t ws_bytes, dpz_stream_t stream);
+int dpz_squant_decode_nodes(int m, const void* table, const void* host_table, uint32_t* status,
+                            dpz_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
