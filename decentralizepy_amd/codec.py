@@ -984,17 +984,27 @@ def _fft_ws(n, workspace, device):
     return buf
 
 
-def _chirp_ws(n, workspace, device):
+def _chirp_ws(n, workspace, device, fused=False):
     workspace = workspace or Workspace(device)
-    buf = workspace.cbuf = fft_chirp_nodes_workspace(1, n, device, getattr(workspace, "cbuf", None))
+    buf = workspace.cbuf = fft_chirp_nodes_workspace(1, n, device, getattr(workspace, "cbuf", None),
+                                                     fused=fused)
     return buf
+
+
+def _chirp_fused(chirp):
+    """``chirp`` of rfft / irfft as ``fused``: "fused" is the only string it takes."""
+    if isinstance(chirp, str) and chirp != "fused":
+        raise ValueError(f"chirp={chirp!r}: True, False or 'fused'")
+    return chirp == "fused"
 
 
 def rfft(x, out=None, workspace=None, chirp=False):
     """``torch.fft.rfft(x)`` of a device fp32 vector (reference sharing/JWINS/FFT.py:12-25):
     the native mixed-radix kernels, or hipFFT for a size with a prime factor above 4096
     (``fft_native(n)``); returns complex64[n // 2 + 1].  ``chirp=True`` (even n >= 4) runs the
-    vector as a one-job table through ``rfft_chirp_nodes`` instead."""
+    vector as a one-job table through ``rfft_chirp_nodes`` instead, ``chirp="fused"`` through
+    ``rfft_chirp_nodes(fused=True)``."""
+    fused = _chirp_fused(chirp)
     _require(x, torch.float32, "x")
     n = x.numel()
     if out is None:
@@ -1004,7 +1014,7 @@ def rfft(x, out=None, workspace=None, chirp=False):
         raise ValueError("out must hold n // 2 + 1 complex values")
     if chirp:
         rfft_chirp_nodes(FftNodesTable([x], None, [out], False, x.device), n,
-                         _chirp_ws(n, workspace, x.device))
+                         _chirp_ws(n, workspace, x.device, fused), fused=fused)
         return out
     ws = _fft_ws(n, workspace, x.device)
     rc = _lib.lib().dpz_rfft(_ptr(x), n, _ptr(out), _ptr(ws), ws.numel(), _stream(x.device))
@@ -1020,7 +1030,9 @@ def fft_native(n):
 def irfft(coeffs, n, out=None, workspace=None, chirp=False):
     """``torch.fft.irfft(coeffs, n)`` (1/n normalisation; reference sharing/JWINS/FFT.py:301).
     ``coeffs`` (complex64[n // 2 + 1]) is overwritten.  ``chirp=True`` (even n >= 4) runs a
-    one-job table through ``irfft_chirp_nodes`` instead, which only reads ``coeffs``."""
+    one-job table through ``irfft_chirp_nodes`` instead, which only reads ``coeffs``;
+    ``chirp="fused"`` through ``irfft_chirp_nodes(fused=True)``."""
+    fused = _chirp_fused(chirp)
     _require(coeffs, torch.complex64, "coeffs")
     n = int(n)
     if coeffs.numel() != n // 2 + 1:
@@ -1030,7 +1042,7 @@ def irfft(coeffs, n, out=None, workspace=None, chirp=False):
     _require(out, torch.float32, "out")
     if chirp:
         irfft_chirp_nodes(IfftNodesTable([coeffs], [out], coeffs.device), n,
-                          _chirp_ws(n, workspace, coeffs.device))
+                          _chirp_ws(n, workspace, coeffs.device, fused), fused=fused)
         return out
     ws = _fft_ws(n, workspace, coeffs.device)
     rc = _lib.lib().dpz_irfft(_ptr(coeffs), n, _ptr(out), _ptr(ws), ws.numel(),
@@ -2122,11 +2134,24 @@ def fft_chirp_length(n):
     return int(_lib.lib().dpz_fft_chirp_length(int(n)))
 
 
-def fft_chirp_nodes_workspace(jobs, n, device, workspace=None):
+def fft_chirp_fused_length(n):
+    """The padded length P of the fused chirp-z transforms of n reals: of the 7-smooth P from
+    n - 1 to the next power of two the one whose plan moves the least (npass * P; a plan with a
+    pass of radix below 16 repacked evenly first); 0 for an n they refuse."""
+    return int(_lib.lib().dpz_fft_chirp_fused_length(int(n)))
+
+
+def _chirp_ws_bytes(jobs, n, fused):
+    name = "dpz_fft_chirp_fused_nodes_workspace_bytes" if fused \
+        else "dpz_fft_chirp_nodes_workspace_bytes"
+    return int(getattr(_lib.lib(), name)(int(jobs), int(n)))
+
+
+def fft_chirp_nodes_workspace(jobs, n, device, workspace=None, fused=False):
     """A uint8 device tensor of ``dpz_fft_chirp_nodes_workspace_bytes(jobs, n)`` bytes
-    (``workspace`` itself when it is large enough); ValueError for a size the chirp-z transforms
-    refuse."""
-    need = int(_lib.lib().dpz_fft_chirp_nodes_workspace_bytes(int(jobs), int(n)))
+    (``fused``: of ``dpz_fft_chirp_fused_nodes_workspace_bytes``; ``workspace`` itself when it is
+    large enough); ValueError for a size the chirp-z transforms refuse."""
+    need = _chirp_ws_bytes(jobs, n, fused)
     if need < 0:
         raise ValueError(f"batched chirp-z real FFTs of n={n}: an even n in [4, 2**30] and "
                          "jobs >= 1")
@@ -2135,10 +2160,12 @@ def fft_chirp_nodes_workspace(jobs, n, device, workspace=None):
     return workspace
 
 
-def _fft_chirp_nodes(name, table, n, workspace, check_rc):
+def _fft_chirp_nodes(name, table, n, workspace, check_rc, fused):
     _require(table.dev, torch.int64, "table")
+    if fused:
+        name = name.replace("_chirp_", "_chirp_fused_")
     if workspace is None:
-        need = int(_lib.lib().dpz_fft_chirp_nodes_workspace_bytes(table.m, int(n)))
+        need = _chirp_ws_bytes(table.m, n, fused)
         workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=table.dev.device)
     rc = getattr(_lib.lib(), name)(table.m, _ptr(table.dev),
                                    ctypes.c_void_p(table.host.ctypes.data), int(n),
@@ -2149,19 +2176,22 @@ def _fft_chirp_nodes(name, table, n, workspace, check_rc):
     return rc
 
 
-def rfft_chirp_nodes(table, n, workspace=None, check_rc=True):
+def rfft_chirp_nodes(table, n, workspace=None, check_rc=True, fused=False):
     """``rfft_nodes``' transforms of ``table`` (an ``FftNodesTable``) by the chirp-z algorithm:
     every even n in [4, 2**30], one launch set whatever the job count.  The results agree with
     ``rfft_nodes``' to rounding (not bit for bit); the x0 subtraction and the accumulating store
     round as ``elementwise(SUB)`` / ``elementwise(ADD)`` do.  ``workspace``:
-    ``fft_chirp_nodes_workspace``'s tensor (allocated here when None)."""
-    return _fft_chirp_nodes("dpz_rfft_chirp_nodes", table, n, workspace, check_rc)
+    ``fft_chirp_nodes_workspace``'s tensor (allocated here when None).  ``fused``: the fused
+    calls (``dpz_rfft_chirp_fused_nodes``: the chirp, the padding and the chirp-spectrum product
+    inside the FFT passes, the padded length ``fft_chirp_fused_length(n)``; a workspace made with
+    ``fused=True``)."""
+    return _fft_chirp_nodes("dpz_rfft_chirp_nodes", table, n, workspace, check_rc, fused)
 
 
-def irfft_chirp_nodes(table, n, workspace=None, check_rc=True):
+def irfft_chirp_nodes(table, n, workspace=None, check_rc=True, fused=False):
     """``irfft_nodes``' transforms of ``table`` (an ``IfftNodesTable``) by the chirp-z algorithm;
-    the coefficients are only read."""
-    return _fft_chirp_nodes("dpz_irfft_chirp_nodes", table, n, workspace, check_rc)
+    the coefficients are only read.  ``fused`` as ``rfft_chirp_nodes``'."""
+    return _fft_chirp_nodes("dpz_irfft_chirp_nodes", table, n, workspace, check_rc, fused)
 
 
 def cplx_chunk_elems():

@@ -151,7 +151,9 @@ struct FtPass {
   uint32_t mnb[FT_MAXSUB], mpp[FT_MAXSUB];  // u / (R / q) and u / pp as umulhi(u, m) (u < 2^16)
   int load_mode;        // 0 complex, 1 real (x, 0), 2 Hermitian extension of n_aux / 2 + 1 values,
                         // 3 the c2r pairing of X[0..n_aux] (even-n inverse, ft_c2r_pair)
+                        // (4: ft_load's NODES mode; 5, 6: its CHIRP modes, set by the kernels)
   int store_mode;       // 0 complex, 1 complex * scale, 2 real part * scale, 3 indices < n_aux only
+                        // (4, 5, 6: ft_store's CHIRP modes)
   int64_t n_aux;
   float scale;
   int inv;
@@ -177,10 +179,48 @@ __device__ __forceinline__ float2 ft_mi(float2 z, bool inv);
 __device__ __forceinline__ float2 ft_c2r_pair(float2 p, float2 q, uint32_t kk, const FtTw& tw);
 __device__ __forceinline__ float2 ft_r2c_pair(float2 p, float2 q, uint32_t kk, const FtTw& tw);
 
+// What the fused chirp-z calls fold into the passes of their two DFT_P (CHIRP, below): the job
+// table, the chirp tables and W_n of the pairing.  `first`: this launch is the forward DFT_P's
+// first pass, whose loads form a = z . w from the job's own rows
+struct FtFuse {
+  const uint64_t* tab;  // forward: {x, x0 or 0, out, accumulate}; inverse: {coeffs, out}
+  const float2* w;      // w_j, j < Lc
+  const float2* bhat;   // DFT_P(b) / P
+  int64_t Lc;           // n / 2
+  FtTw twn;
+  float scale;          // inverse: 1 / n
+  int inverse;
+  int first;
+};
+
 // NODES (the batched kernels only): load mode 4, z[i] - z0[i] per component (the real vectors x and
-// x0 as n / 2 pairs: one fp32 subtraction per element, dpz_elementwise(SUB)'s), z0 behind in_re
-template <bool NODES>
-__device__ __forceinline__ float2 ft_load(const FtPass& a, const FtIo& io, int64_t i) {
+// x0 as n / 2 pairs: one fp32 subtraction per element, dpz_elementwise(SUB)'s), z0 behind in_re.
+// CHIRP (the fused chirp-z kernels only): load modes 5 and 6, ft_chirp_pre_kernel's a[i] - for
+// i < Lc (z[i] - z0[i]) w_i, z0 behind in_re where the job has one (5), or the c2r pairing of
+// X[i] and X[Lc - i] times conj w_i (6); for i >= Lc an exact 0 and no load at all
+template <bool NODES, bool CHIRP = false>
+__device__ __forceinline__ float2 ft_load(const FtPass& a, const FtIo& io, const FtFuse* fx,
+                                          int64_t i) {
+  if constexpr (CHIRP) {
+    if (io.load_mode >= 5) {
+      if (i >= fx->Lc) return make_float2(0.0f, 0.0f);
+      const float2 w = fx->w[i];
+      if (io.load_mode == 6) {
+        float2 p = io.in[i], q = io.in[fx->Lc - i];
+        if (i == 0) {
+          p.y = 0.0f;
+          q.y = 0.0f;
+        }
+        return ft_cmul(ft_c2r_pair(p, q, (uint32_t)i, fx->twn), make_float2(w.x, -w.y));
+      }
+      float2 u = io.in[i];
+      if (io.in_re) {
+        const float2 u0 = reinterpret_cast<const float2*>(io.in_re)[i];
+        u = make_float2(u.x - u0.x, u.y - u0.y);
+      }
+      return ft_cmul(u, w);
+    }
+  }
   if constexpr (NODES) {
     if (io.load_mode == 4) {
       const float2 u = io.in[i], v = reinterpret_cast<const float2*>(io.in_re)[i];
@@ -208,7 +248,30 @@ __device__ __forceinline__ float2 ft_load(const FtPass& a, const FtIo& io, int64
   return io.in[i];
 }
 
-__device__ __forceinline__ void ft_store(const FtPass& a, const FtIo& io, int64_t o, float2 v) {
+// CHIRP: store mode 4, ft_chirp_mul_kernel's v Bhat[o] (conj Bhat for inverse jobs); 5 and 6, the
+// last pass of the inverse DFT_P, indices < Lc only: v w_o into the job's row (5, forward jobs:
+// the pairing follows) or (v conj w_o) / n into its output row (6, ft_chirp_post_c2r_kernel's)
+template <bool CHIRP = false>
+__device__ __forceinline__ void ft_store(const FtPass& a, const FtIo& io, const FtFuse* fx,
+                                         int64_t o, float2 v) {
+  if constexpr (CHIRP) {
+    if (a.store_mode == 4) {
+      const float2 b = fx->bhat[o];
+      io.out[o] = ft_cmul(v, fx->inverse ? make_float2(b.x, -b.y) : b);
+      return;
+    }
+    if (a.store_mode >= 5) {
+      if (o >= fx->Lc) return;
+      const float2 w = fx->w[o];
+      if (a.store_mode == 5) {
+        io.out[o] = ft_cmul(v, w);
+      } else {
+        const float2 z = ft_cmul(v, make_float2(w.x, -w.y));
+        io.out[o] = make_float2(z.x * fx->scale, z.y * fx->scale);
+      }
+      return;
+    }
+  }
   switch (a.store_mode) {
     case 1: io.out[o] = make_float2(v.x * a.scale, v.y * a.scale); break;
     case 2: io.out_re[o] = v.x * a.scale; break;
@@ -435,8 +498,9 @@ __device__ __forceinline__ void ft_sub_any(const float2* src, float2* dst, int B
 // through registers run with ONE LDS buffer (sub-passes staged in registers): 72 VGPRs and half
 // the LDS, so more blocks per CU; the others (11, 13, other primes) ping-pong two buffers
 extern __shared__ float2 ft_lds[];
-template <bool IP, bool NODES = false>
-__device__ __forceinline__ void ft_pass_body(const FtPass& a, const FtIo& io) {
+template <bool IP, bool NODES = false, bool CHIRP = false>
+__device__ __forceinline__ void ft_pass_body(const FtPass& a, const FtIo& io,
+                                             const FtFuse* fx = nullptr) {
   const int B = a.B, R = a.R, RP = a.RP;
   const int t = threadIdx.x;
   // pair mode: slots c < H hold columns jf0 + c (jf <= S / 2), slots H + c their mirrors S - jf
@@ -478,7 +542,7 @@ __device__ __forceinline__ void ft_pass_body(const FtPass& a, const FtIo& io) {
       for (int i = 0; i < FT_REG_ELEMS / FT_THREADS; ++i) {
         const int r = r0 + i * rs;
         const bool ok = cv && r < R;
-        v[i] = ft_load<NODES>(a, io, ok ? j + (int64_t)r * a.S : j0);
+        v[i] = ft_load<NODES, CHIRP>(a, io, fx, ok ? j + (int64_t)r * a.S : j0);
         const uint32_t e = ok ? (uint32_t)(((uint64_t)r * k) * twm) : 0u;
         w[i] = ft_root(a.tw, e, inv);
       }
@@ -489,7 +553,7 @@ __device__ __forceinline__ void ft_pass_body(const FtPass& a, const FtIo& io) {
       }
     } else if (cv) {
       for (int r = r0; r < R; r += rs) {
-        float2 v = ft_load<NODES>(a, io, j + (int64_t)r * a.S);
+        float2 v = ft_load<NODES, CHIRP>(a, io, fx, j + (int64_t)r * a.S);
         if (k && r) v = ft_cmul(v, ft_root(a.tw, (uint32_t)(((uint64_t)r * k) * twm), inv));
         src[c * RP + r] = v;
       }
@@ -568,12 +632,12 @@ __device__ __forceinline__ void ft_pass_body(const FtPass& a, const FtIo& io) {
       for (int i = 0; i < NE; ++i) {
         const int e = t + i * FT_THREADS;
         const int c = e / R, m = e - c * R;
-        if (c < cols) ft_store(a, io, (j0 + c) * R + m, v[i]);
+        if (c < cols) ft_store<CHIRP>(a, io, fx, (j0 + c) * R + m, v[i]);
       }
     } else {
       for (int e = t; e < cols * R; e += FT_THREADS) {
         const int c = e / R, m = e - c * R;
-        ft_store(a, io, (j0 + c) * R + m, src[c * RP + m]);
+        ft_store<CHIRP>(a, io, fx, (j0 + c) * R + m, src[c * RP + m]);
       }
     }
   } else {
@@ -592,11 +656,12 @@ __device__ __forceinline__ void ft_pass_body(const FtPass& a, const FtIo& io) {
 #pragma unroll
         for (int i = 0; i < NE; ++i) {
           const int m = m0 + i * rs;
-          if (m < R) ft_store(a, io, base + (int64_t)m * a.p, v[i]);
+          if (m < R) ft_store<CHIRP>(a, io, fx, base + (int64_t)m * a.p, v[i]);
         }
       }
     } else if (c < cols) {
-      for (int m = m0; m < R; m += rs) ft_store(a, io, base + (int64_t)m * a.p, src[c * RP + m]);
+      for (int m = m0; m < R; m += rs)
+        ft_store<CHIRP>(a, io, fx, base + (int64_t)m * a.p, src[c * RP + m]);
     }
   }
 }
@@ -673,6 +738,34 @@ ft_pass_ip_rows_kernel(FtPass a, size_t pitch) {
 }
 __global__ void __launch_bounds__(FT_THREADS) ft_pass_rows_kernel(FtPass a, size_t pitch) {
   ft_pass_body<false>(a, ft_io_row(a, pitch));
+}
+
+// ---- the rows kernels of the fused chirp-z calls: the same pass bodies between the same rows,
+// with the chirp, the padding and the Bhat product in their loads and stores (ft_load's and
+// ft_store's CHIRP modes).  The forward DFT_P's first pass reads the job's own rows (forward jobs:
+// x and x0; inverse jobs: the coefficients) and no workspace row; the inverse DFT_P's last pass
+// of an inverse job writes its output row.  Which job is which comes from the table, so one launch
+// serves any mix of rows.
+template <bool IP>
+__device__ __forceinline__ void ft_pass_fused_body(const FtPass& a, size_t pitch,
+                                                   const FtFuse& fx) {
+  FtIo io = ft_io_row(a, pitch);
+  const uint64_t* e = fx.tab + (size_t)blockIdx.y * (fx.inverse ? 2 : 4);
+  if (fx.first) {
+    io.in = reinterpret_cast<const float2*>(e[0]);
+    io.in_re = fx.inverse ? nullptr : reinterpret_cast<const float*>(e[1]);
+    io.load_mode = fx.inverse ? 6 : 5;
+  }
+  if (a.store_mode == 6) io.out = reinterpret_cast<float2*>(e[1]);
+  ft_pass_body<IP, false, true>(a, io, &fx);
+}
+__global__ void __launch_bounds__(FT_THREADS) __attribute__((amdgpu_waves_per_eu(DPZ_FT_IP_WAVES, 8)))
+ft_pass_ip_fused_kernel(FtPass a, size_t pitch, FtFuse fx) {
+  ft_pass_fused_body<true>(a, pitch, fx);
+}
+__global__ void __launch_bounds__(FT_THREADS)
+ft_pass_fused_kernel(FtPass a, size_t pitch, FtFuse fx) {
+  ft_pass_fused_body<false>(a, pitch, fx);
 }
 
 // even n, forward: X[k] = ((Z[k] + conj Z[M-k]) - i W_n^k (Z[k] - conj Z[M-k])) / 2 for the pair
@@ -883,17 +976,39 @@ static int ft_rows_lds_attr() {
   return DPZ_OK;
 }
 
+// the fused rows kernels' attribute, per device like the rows kernels' (guarded by g_ft_mu)
+static std::set<int> g_ft_fused_lds_devs;
+
+static int ft_fused_lds_attr() {
+  int dev = 0;
+  DPZ_HIP_TRY(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(g_ft_mu);
+  if (g_ft_fused_lds_devs.count(dev)) return DPZ_OK;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(ft_pass_fused_kernel),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void*>(ft_pass_ip_fused_kernel),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+    return DPZ_ERR_INTERNAL;
+  g_ft_fused_lds_devs.insert(dev);
+  return DPZ_OK;
+}
+
 // the plan's passes: pass 1 reads (in, in_re, load_mode), the last writes (out, out_re,
 // store_mode, scale); the others alternate between bufA and bufB so that the last lands in out.
-// rows_pitch != 0: `jobs` transforms, the pointers being job 0's rows (ft_pass_rows_kernel)
+// rows_pitch != 0: `jobs` transforms, the pointers being job 0's rows (ft_pass_rows_kernel);
+// with `fuse` the fused rows kernels: fuse->first asks pass 1 to load from the job's rows (`in` is
+// not read), store_mode is one of ft_store's CHIRP modes
 static int ft_run(const FtPlan& pl, const FtTw& tw, bool inv, const float2* in, const float* in_re,
                   int load_mode, float2* out, float* out_re, int store_mode, float scale,
                   int64_t n_aux, float2* bufA, float2* bufB, hipStream_t st,
                   bool* pair_last = nullptr, const FtNodes* nodes = nullptr, int jobs = 0,
-                  size_t rows_pitch = 0) {
+                  size_t rows_pitch = 0, const FtFuse* fuse = nullptr) {
   const bool want_pair = pair_last && *pair_last;
   if (pair_last) *pair_last = false;
-  if (rows_pitch) {
+  if (fuse) {
+    const int rc = ft_fused_lds_attr();
+    if (rc != DPZ_OK) return rc;
+  } else if (rows_pitch) {
     const int rc = ft_rows_lds_attr();
     if (rc != DPZ_OK) return rc;
   } else if (nodes && !g_ft_nodes_lds_set) {
@@ -969,7 +1084,18 @@ static int ft_run(const FtPlan& pl, const FtTw& tw, bool inv, const float2* in, 
     }
     const size_t lds = ((ip ? 1 : 2) * (size_t)B * a.RP + (a.R <= FT_PACK ? a.R : 0)) *
                        sizeof(float2);
-    if (rows_pitch) {
+    if (fuse) {
+      FtFuse fx = *fuse;
+      fx.first = first && fuse->first;
+      const dim3 grid((unsigned)blocks, (unsigned)jobs);
+      if (ip) {
+        DPZ_TIMED(DPZ_KT_FFT, st,
+                  ft_pass_ip_fused_kernel<<<grid, FT_THREADS, lds, st>>>(a, rows_pitch, fx));
+      } else {
+        DPZ_TIMED(DPZ_KT_FFT, st,
+                  ft_pass_fused_kernel<<<grid, FT_THREADS, lds, st>>>(a, rows_pitch, fx));
+      }
+    } else if (rows_pitch) {
       const dim3 grid((unsigned)blocks, (unsigned)jobs);
       if (ip) {
         DPZ_TIMED(DPZ_KT_FFT, st,
@@ -1333,8 +1459,10 @@ __global__ void __launch_bounds__(256) ft_chirp_mul_kernel(FtChirp c) {
     a[i] = ft_cmul(a[i], ft_conj_if(c.bhat[i], c.inverse != 0));
 }
 
-// forward: Z[k] = y[k] w_k, then ft_r2c_post_nodes_kernel's pairing and store
-__global__ void __launch_bounds__(256) ft_chirp_post_r2c_kernel(FtChirp c, FtTw twn) {
+// forward: Z[k] = y[k] w_k (MULW; the fused call's last pass has stored Z itself), then
+// ft_r2c_post_nodes_kernel's pairing and store
+template <bool MULW>
+__device__ __forceinline__ void ft_chirp_post_r2c_body(const FtChirp& c, const FtTw& twn) {
   const uint64_t* e = c.tab + (size_t)blockIdx.y * 4;
   const float2* y = reinterpret_cast<const float2*>(c.row + (size_t)blockIdx.y * c.pitch);
   float2* out = reinterpret_cast<float2*>(e[2]);
@@ -1348,18 +1476,25 @@ __global__ void __launch_bounds__(256) ft_chirp_post_r2c_kernel(FtChirp c, FtTw 
     out[i] = v;
   };
   for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k <= M / 2; k += (int64_t)gridDim.x * 256) {
+    auto z = [&](int64_t i) { return MULW ? ft_cmul(y[i], c.w[i]) : y[i]; };
     if (k == 0) {
-      const float2 z0 = ft_cmul(y[0], c.w[0]);
+      const float2 z0 = z(0);
       put(0, make_float2(z0.x + z0.y, 0.0f));
       put(M, make_float2(z0.x - z0.y, 0.0f));
       continue;
     }
-    const float2 a = ft_cmul(y[k], c.w[k]), b = ft_cmul(y[M - k], c.w[M - k]);
+    const float2 a = z(k), b = z(M - k);
     const float2 xk = ft_r2c_pair(a, b, (uint32_t)k, twn);
     const float2 xm = ft_r2c_pair(b, a, (uint32_t)(M - k), twn);
     put(k, xk);
     if (M - k != k) put(M - k, xm);
   }
+}
+__global__ void __launch_bounds__(256) ft_chirp_post_r2c_kernel(FtChirp c, FtTw twn) {
+  ft_chirp_post_r2c_body<true>(c, twn);
+}
+__global__ void __launch_bounds__(256) ft_chirp_pair_kernel(FtChirp c, FtTw twn) {
+  ft_chirp_post_r2c_body<false>(c, twn);
 }
 
 // inverse: the n reals as L pairs, out[k] = y[k] conj w_k / n
@@ -1566,6 +1701,200 @@ extern "C" int dpz_irfft_chirp_nodes(int jobs, const void* table, const void* ho
                                      int64_t n, void* ws, size_t ws_bytes, dpz_stream_t stream) {
   return ft_chirp_nodes(jobs, table, host_table, 2, n, ws, ws_bytes,
                         static_cast<hipStream_t>(stream));
+}
+
+// ---- fused chirp-z: a padded length chosen by what its plan moves, the chirp, the padding and the
+// Bhat product inside the passes ------------------------------------------------------------------
+// Every pass moves P complex per job, so a plan costs npass * P; ft_make_plan's greedy packing can
+// leave a runt, a pass of radix below 16 whose 256-thread blocks hold at most 16 * 15 elements
+// (90,000 = 250 * 180 * 2: blocks of 32).  A plan of one pass is never a runt.
+static bool ft_plan_has_runt(const FtPlan& pl) {
+  for (int s = 0; s < pl.npass && pl.npass >= 2; ++s)
+    if (pl.R[s] < 16) return true;
+  return false;
+}
+
+// rem as k radices lo <= r[0] <= ... <= r[k - 1] <= FT_PACK, the smallest as large as it can be,
+// then the next smallest, and so on (the first hit of a descending search); false when there is
+// no such split
+static bool ft_balanced_split(int64_t rem, int k, int64_t lo, int* r) {
+  if (k == 1) {
+    if (rem < lo || rem > FT_PACK) return false;
+    r[0] = (int)rem;
+    return true;
+  }
+  for (int64_t a = FT_PACK; a >= lo; --a) {
+    if (rem % a != 0) continue;
+    int64_t t = 1;  // a^k <= rem, or a cannot be the smallest of k radices
+    for (int i = 0; i < k && t <= rem; ++i) t *= a;
+    if (t > rem) continue;
+    if (ft_balanced_split(rem / a, k - 1, a, r + 1)) {
+      r[0] = (int)a;
+      return true;
+    }
+  }
+  return false;
+}
+
+// The balanced packer (the fused chirp-z calls only; ft_make_plan and the native plans are not
+// touched): P's prime factors in `npass` passes, every radix <= FT_PACK, the smallest radix
+// maximal.  Ties: of two packings the one whose radices, sorted ascending, are lexicographically
+// larger - the second smallest radix maximal, then the third, ... - which leaves one multiset of
+// radices; the passes take them in descending order (as the greedy bins mostly come out).
+// Sub-passes as ft_make_plan's: the odd primes, largest first, then the 2s as radix 8 / 4 / 2.
+static bool ft_balanced_plan(int64_t P, int npass, FtPlan* pl) {
+  int r[FT_MAXPASS];
+  if (npass < 1 || npass > FT_MAXPASS || !ft_balanced_split(P, npass, 2, r)) return false;
+  pl->L = P;
+  pl->npass = npass;
+  for (int s = 0; s < npass; ++s) {
+    int R = r[npass - 1 - s], ns = 0, twos = 0;
+    pl->R[s] = R;
+    for (int f : {7, 5, 3})
+      for (; R % f == 0; R /= f) {
+        if (ns == FT_MAXSUB) return false;
+        pl->q[s][ns++] = f;
+      }
+    for (; R % 2 == 0; R /= 2) ++twos;
+    if (R != 1) return false;  // not 7-smooth
+    while (twos > 0) {
+      const int take = twos >= 3 ? 3 : twos;
+      if (ns == FT_MAXSUB) return false;
+      pl->q[s][ns++] = 1 << take;
+      twos -= take;
+    }
+    pl->nsub[s] = ns;
+  }
+  return true;
+}
+
+// the plan the fused calls run a candidate P with: the greedy one, or the balanced one of as many
+// passes where the greedy one has a runt
+static bool ft_fused_plan_of(int64_t P, FtPlan* pl) {
+  if (!ft_make_plan(P, pl) || pl->npass < 1) return false;
+  if (ft_plan_has_runt(*pl)) {
+    FtPlan bal;
+    if (ft_balanced_plan(P, pl->npass, &bal)) *pl = bal;
+  }
+  return true;
+}
+
+// The padded length and plan of an even n in [4, 2^30] (false for any other n): of every 7-smooth
+// P with n - 1 <= P <= the next power of two (ft_chirp_len's candidates: one per odd part, since
+// that power of two is below 2 (n - 1)) the one with the smallest npass * P, the smaller P on a
+// tie.  A pure function of n, cached per n.
+static std::mutex g_ft_fused_mu;
+static std::map<int64_t, FtPlan> g_ft_fused_plans;
+
+static bool ft_chirp_fused_plan(int64_t n, FtPlan* out) {
+  if (n < 4 || n % 2 != 0 || n > (int64_t(1) << 30)) return false;
+  std::lock_guard<std::mutex> lock(g_ft_fused_mu);
+  auto it = g_ft_fused_plans.find(n);
+  if (it == g_ft_fused_plans.end()) {
+    const int64_t lo = n - 1;
+    int64_t top = 1;
+    while (top < lo) top <<= 1;
+    FtPlan best, pl;
+    int64_t best_cost = 0;
+    for (int64_t p7 = 1; p7 <= top; p7 *= 7)
+      for (int64_t p5 = p7; p5 <= top; p5 *= 5)
+        for (int64_t p3 = p5; p3 <= top; p3 *= 3) {
+          int64_t p = p3;
+          while (p < lo) p <<= 1;
+          if (p > top || !ft_fused_plan_of(p, &pl)) continue;
+          const int64_t cost = pl.npass * p;
+          if (best_cost == 0 || cost < best_cost || (cost == best_cost && p < best.L)) {
+            best = pl;
+            best_cost = cost;
+          }
+        }
+    if (best_cost == 0) return false;
+    it = g_ft_fused_plans.emplace(n, best).first;
+  }
+  *out = it->second;
+  return true;
+}
+
+extern "C" int64_t dpz_fft_chirp_fused_length(int64_t n) {
+  FtPlan pl;
+  return ft_chirp_fused_plan(n, &pl) ? pl.L : 0;
+}
+
+extern "C" int64_t dpz_fft_chirp_fused_nodes_workspace_bytes(int jobs, int64_t n) {
+  const int64_t P = dpz_fft_chirp_fused_length(n);
+  if (jobs < 1 || P == 0) return -1;
+  return (int64_t)((size_t)jobs * ft_chirp_pitch(P) * 2 + 256);
+}
+
+// The unfused chain without its three elementwise launches: the forward DFT_P's first pass forms a
+// as it loads (no row is written first, and the zero padding is never read), its last pass stores
+// the product with Bhat, the inverse DFT_P's last pass stores y w_k into row 0 (forward jobs) or
+// (y conj w_k) / n into the output row (inverse jobs) for k < L only.  The forward pairing needs
+// Z[k] and Z[L - k], which different blocks of that pass hold: one launch of its own.
+static int ft_chirp_fused_nodes(int jobs, const void* table, const void* host_table, int words,
+                                int64_t n, void* ws, size_t ws_bytes, hipStream_t st) {
+  if (jobs < 1 || !table || !host_table || (reinterpret_cast<uintptr_t>(table) & 7u))
+    return DPZ_ERR_ARG;
+  FtPlan pl;
+  if (!ft_chirp_fused_plan(n, &pl)) return DPZ_ERR_UNSUPPORTED;
+  const int64_t P = pl.L;
+  int rc = ft_nodes_rows(jobs, host_table, words);
+  if (rc != DPZ_OK) return rc;
+  if (jobs > 65535) return DPZ_ERR_UNSUPPORTED;
+  if (!ws || (int64_t)ws_bytes < dpz_fft_chirp_fused_nodes_workspace_bytes(jobs, n))
+    return DPZ_ERR_WORKSPACE;
+  FtTw twn, twp;
+  dpz::FtChirpTab ct;
+  if ((rc = ft_tables((uint32_t)n, &twn)) != DPZ_OK || (rc = ft_tables((uint32_t)P, &twp)) != DPZ_OK ||
+      (rc = dpz::ft_chirp_tables(n, P, &ct)) != DPZ_OK)
+    return rc;
+  const bool inverse = words == 2;
+  const size_t pitch = ft_chirp_pitch(P);
+  FtFuse fx{};
+  fx.tab = static_cast<const uint64_t*>(table);
+  fx.w = ct.w;
+  fx.bhat = ct.bhat;
+  fx.Lc = n / 2;
+  fx.twn = twn;
+  fx.scale = 1.0f / (float)n;
+  fx.inverse = inverse ? 1 : 0;
+  // the rows as the unfused call's: DFT_P leaves row (npass & 1), the inverse DFT_P comes back to
+  // row 0 (inverse jobs: its last pass leaves the workspace)
+  char* r0 = reinterpret_cast<char*>(ft_align(ws, 0));
+  char* r1 = r0 + (size_t)jobs * pitch;
+  float2* row0 = reinterpret_cast<float2*>(r0);
+  float2* mid = reinterpret_cast<float2*>((pl.npass & 1) ? r1 : r0);
+  float2* oth = reinterpret_cast<float2*>((pl.npass & 1) ? r0 : r1);
+  fx.first = 1;
+  rc = ft_run(pl, twp, false, row0, nullptr, 0, mid, nullptr, 4, 1.0f, 0, oth, mid, st, nullptr,
+              nullptr, jobs, pitch, &fx);
+  if (rc != DPZ_OK) return rc;
+  fx.first = 0;
+  rc = ft_run(pl, twp, true, mid, nullptr, 0, row0, nullptr, inverse ? 6 : 5, 1.0f, 0,
+              reinterpret_cast<float2*>(r1), row0, st, nullptr, nullptr, jobs, pitch, &fx);
+  if (rc != DPZ_OK || inverse) return rc;
+  dpz::FtChirp c{};
+  c.tab = fx.tab;
+  c.row = r0;
+  c.pitch = pitch;
+  c.L = fx.Lc;
+  const dim3 g(grid_for(c.L / 2 + 1), (unsigned)jobs);
+  DPZ_TIMED(DPZ_KT_FFT, st, dpz::ft_chirp_pair_kernel<<<g, 256, 0, st>>>(c, twn));
+  return DPZ_OK;
+}
+
+extern "C" int dpz_rfft_chirp_fused_nodes(int jobs, const void* table, const void* host_table,
+                                          int64_t n, void* ws, size_t ws_bytes,
+                                          dpz_stream_t stream) {
+  return ft_chirp_fused_nodes(jobs, table, host_table, 4, n, ws, ws_bytes,
+                              static_cast<hipStream_t>(stream));
+}
+
+extern "C" int dpz_irfft_chirp_fused_nodes(int jobs, const void* table, const void* host_table,
+                                           int64_t n, void* ws, size_t ws_bytes,
+                                           dpz_stream_t stream) {
+  return ft_chirp_fused_nodes(jobs, table, host_table, 2, n, ws, ws_bytes,
+                              static_cast<hipStream_t>(stream));
 }
 
 extern "C" int dpz_cplx_key(const float* change, float* acc, int acc_mode, int64_t m, float* key,

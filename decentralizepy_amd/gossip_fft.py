@@ -39,7 +39,9 @@ the batched selection and fold still apply.  A batched hipFFT plan is not offere
 ``chirp=True`` such a size runs the three transform legs through ``dpz_rfft_chirp_nodes`` /
 ``dpz_irfft_chirp_nodes`` on the same tables instead (the chirp-z algorithm: one launch set per
 leg again); ``batched`` says whether the transforms run as launch sets, ``native`` stays
-``codec.fft_native(N)``.  At a size with a native plan ``chirp`` changes nothing.
+``codec.fft_native(N)``.  ``chirp="fused"`` runs those legs on the fused chirp-z calls
+(``dpz_rfft_chirp_fused_nodes`` / ``dpz_irfft_chirp_fused_nodes``: fewer launches, a padded length
+chosen by what its plan moves).  At a size with a native plan ``chirp`` changes nothing.
 
 Ties at the k-th key go to the lowest indices; finite models only.  The device FFT rounds
 differently from the reference's pocketfft, so parity with the reference is a tolerance parity
@@ -77,8 +79,8 @@ class FftRound(ShardedRound):
             raise ValueError(
                 f"unknown arguments {sorted(unknown)}: FftRound offers neither compressed "
                 "payloads nor another exchange than the all-gather")
-        if not isinstance(chirp, bool):
-            raise ValueError(f"chirp={chirp!r}: True or False")
+        if not isinstance(chirp, bool) and chirp != "fused":
+            raise ValueError(f"chirp={chirp!r}: True, False or 'fused'")
         if not change_based_selection:
             raise ValueError("change_based_selection=False (selection by |F(x)|) is not "
                              "offered: use the per-node plugin sharing.JWINS.FFT")
@@ -137,7 +139,9 @@ class FftRound(ShardedRound):
         from . import codec
         dev, m, M, N, k = self.device, self.m, self.M, self.N, self.k
         self.native = codec.fft_native(N)
-        self.batched = self.native or self.chirp
+        self.batched = self.native or bool(self.chirp)
+        # the chirp-z calls' keyword (a native size runs the native calls, which have none)
+        self._ckw = {"fused": True} if self.chirp == "fused" and not self.native else {}
         xs, x0s = list(self.x), list(self.x0)
         if self.batched:
             self._pre = codec.FftNodesTable(xs + xs, [None] * m + x0s,
@@ -148,7 +152,7 @@ class FftRound(ShardedRound):
             if self.native:
                 self._fws = codec.fft_nodes_workspace(2 * m, N, dev)
             else:  # the same tables through the chirp-z entry points
-                self._fws = codec.fft_chirp_nodes_workspace(2 * m, N, dev)
+                self._fws = codec.fft_chirp_nodes_workspace(2 * m, N, dev, **self._ckw)
         else:
             self._fft_ws = codec.Workspace(dev)
             self._diff = torch.empty(N, dtype=torch.float32, device=dev)
@@ -207,12 +211,12 @@ class FftRound(ShardedRound):
     def _rfft_nodes(self, table):
         from . import codec
         call = codec.rfft_nodes if self.native else codec.rfft_chirp_nodes
-        call(table, self.N, self._fws)
+        call(table, self.N, self._fws, **self._ckw)
 
     def _irfft_nodes(self, table):
         from . import codec
         call = codec.irfft_nodes if self.native else codec.irfft_chirp_nodes
-        call(table, self.N, self._fws)
+        call(table, self.N, self._fws, **self._ckw)
 
     # ---- the legs of a round -----------------------------------------------------------------
     def encode(self):

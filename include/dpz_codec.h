@@ -1231,6 +1231,30 @@ int dpz_rfft_chirp_nodes(int jobs, const void* table, const void* host_table, in
                          size_t ws_bytes, dpz_stream_t stream);
 int dpz_irfft_chirp_nodes(int jobs, const void* table, const void* host_table, int64_t n, void* ws,
                           size_t ws_bytes, dpz_stream_t stream);
+/* ---- Fused chirp-z real FFTs ---------------------------------------------------------------------
+ * dpz_rfft_chirp_fused_nodes / dpz_irfft_chirp_fused_nodes: the chirp-z calls above - the same
+ * tables, argument checks, status codes, chirp tables and two workspace rows per job - with the
+ * chirp, the zero padding and the product with DFT_P(b) / P inside the passes of the two DFT_P
+ * instead of three elementwise launches: the forward DFT_P's first pass forms a = z . w as it loads
+ * (the padding is an exact 0 that is never read), its last pass stores the product, the inverse
+ * DFT_P's last pass stores y w_k (forward jobs; one pairing launch follows) or (y conj w_k) / n
+ * (inverse jobs, into the output row) for k < L only.  2 npass + 1 launches forward, 2 npass
+ * inverse, whatever `jobs` is.  Every folded operation is the elementwise kernel's, on the same
+ * operands in the same order: where P and the plan are those of the unfused call the result is
+ * bit for bit its result.
+ * P = dpz_fft_chirp_fused_length(n) (0 for an n the calls refuse) is chosen by what the plan moves:
+ * of every 7-smooth P with n - 1 <= P <= the next power of two the one with the smallest
+ * npass(P) * P, the smaller P on a tie.  A candidate runs the native packing of its passes unless
+ * that has two or more passes and one of radix below 16; then it runs a balanced packing of as
+ * many passes, every radix <= 256 and the smallest radix as large as it can be (89,834: 90,000 =
+ * 50 * 45 * 40, where the native packing is 250 * 180 * 2).
+ * ws: dpz_fft_chirp_fused_nodes_workspace_bytes(jobs, n) DEVICE bytes (-1 where refused).        */
+int64_t dpz_fft_chirp_fused_length(int64_t n);
+int64_t dpz_fft_chirp_fused_nodes_workspace_bytes(int jobs, int64_t n);
+int dpz_rfft_chirp_fused_nodes(int jobs, const void* table, const void* host_table, int64_t n,
+                               void* ws, size_t ws_bytes, dpz_stream_t stream);
+int dpz_irfft_chirp_fused_nodes(int jobs, const void* table, const void* host_table, int64_t n,
+                                void* ws, size_t ws_bytes, dpz_stream_t stream);
 int64_t dpz_cplx_chunk_elems(void);
 size_t dpz_cplx_encode_workspace_bytes(int m, int64_t n);
 int dpz_cplx_encode_nodes(int m, const void* node_table, int64_t n, int64_t k, int acc_mode,

@@ -39,6 +39,9 @@ launch sets) against ``FftRound()`` (reported as ``baseline``: hipFFT node after
 two algorithms for the same transforms, so what is checked is that their F(x) of the first round
 (from equal models) agree to 1e-5 of the largest coefficient; a selection whose k-th and
 (k + 1)-th keys lie closer than the rounding may differ, and the models then go their own way.
+``--chirp fused`` adds ``FftRound(chirp="fused")`` (reported as ``fused``) as a third engine in
+the same alternation, checked the same way, with its speed-up over ``engine`` per leg
+(``*_fused_speedup``: [engine min / fused max, engine max / fused min]).
 """
 import argparse
 import json
@@ -201,6 +204,8 @@ def run_shape(args, name, dev):
     noise = torch.randn(n, device=dev, generator=gen)  # the "training" step, rolled per node
     if args.chirp:  # the chirp-z engine against the same engine without the keyword
         variants = {"engine": Engine(adj, x0, dev, chirp=True), "baseline": Engine(adj, x0, dev)}
+        if args.chirp == "fused":
+            variants = {"fused": Engine(adj, x0, dev, chirp="fused"), **variants}
     else:
         variants = {"engine": Engine(adj, x0, dev), "baseline": Baseline(adj, x0, dev)}
     del x0
@@ -218,8 +223,8 @@ def run_shape(args, name, dev):
             timed_round(obj)
         r += 1
         torch.cuda.synchronize()
-        if args.chirp and r == 1 and not close_state(eng, base, m):
-            raise SystemExit(f"{name}: the two engines' F(x) of the first round differ by more "
+        if args.chirp and r == 1 and not all(close_state(v, base, m) for v in variants.values()):
+            raise SystemExit(f"{name}: the engines' F(x) of the first round differ by more "
                              "than rounding; nothing was timed")
     if not args.chirp and not same_state(eng, base, m):
         raise SystemExit(f"{name}: the engine's and the baseline's states differ after two "
@@ -256,6 +261,11 @@ def run_shape(args, name, dev):
     for leg in ("encode", "fold", "post", "device_ms", "host_ms", "wall_ms"):
         res[f"{leg}_speedup"] = [round(b[leg]["min_ms"] / e[leg]["max_ms"], 2),
                                  round(b[leg]["max_ms"] / e[leg]["min_ms"], 2)]
+    if "fused" in res:
+        for leg in ("encode", "fold", "post", "device_ms", "host_ms", "wall_ms"):
+            f = res["fused"][leg]
+            res[f"{leg}_fused_speedup"] = [round(e[leg]["min_ms"] / f["max_ms"], 2),
+                                           round(e[leg]["max_ms"] / f["min_ms"], 2)]
     print(json.dumps(res), flush=True)
     if same is False:
         raise SystemExit(f"{name}: the engine's and the baseline's states differ")
@@ -267,9 +277,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=0, help="0: the shape's own count")
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--chirp", action="store_true",
+    ap.add_argument("--chirp", nargs="?", const=True, default=False, choices=[True, "fused"],
                     help="time FftRound(chirp=True) (as 'engine') against FftRound() (as "
-                         "'baseline'); their states agree to rounding, not bit for bit")
+                         "'baseline'); their states agree to rounding, not bit for bit.  "
+                         "'--chirp fused': FftRound(chirp='fused') (as 'fused') as well")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_fft_round needs a ROCm GPU; there is no CPU path")
